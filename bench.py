@@ -18,8 +18,13 @@ Data: synthetic, resident in HBM before timing (fp16 weights, counter-hash, std 
 activations, unit variance with 1 % x20 outlier channels).  One activation tensor per input
 width is shared by the units of that width on a rank; every unit still computes its own Gram.
 
-`extra` carries the single-layer numbers (s/layer and cols/s of the 4096x4096 q_proj layer at
-N = 262144 and N = 2048, one hipGraph replay each).  `--workload layer` times that single layer
+A plain run sets up, warms up, times `--steps` steps and prints the line (metric, value, unit,
+ms_per_step, ...); `--dump-outputs DIR` also writes what the last timed step returned (dump_outputs).
+Everything measured beside the headline figure runs only with `--full`: `roofline` (the Gram alone,
+the live stage rooflines), `cpu_baseline`, and `extra` -- the single-layer numbers (s/layer and
+cols/s of the 4096x4096 q_proj layer at N = 262144 and N = 2048, one hipGraph replay each), the
+transfer-inclusive step (h2d), the 8-rank shard projection (shards8), the layer-by-layer decoder
+flow (decoder) and a short run of every other config (configs).  `--workload layer` times that single layer
 per rank instead (weak scaling, the round-1 bench line).  `--workload split --n 4096 --m 11008`
 times ONE layer whose Gram is split over the ranks' calibration rows (strong scaling, SURVEY
 §8e(ii): sharding.quantize_layer_split — partial Grams, rank-ordered fold on rank 0, the rest of
@@ -62,8 +67,17 @@ def parse(argv=None):
     p.add_argument("--share-gpu", action="store_true",
                    help="TESTING ONLY: every rank on cuda:0 with the gloo backend (the real kernels and the "
                         "sharded step's gather on a one-GPU box; not a scaling measurement)")
-    p.add_argument("--steps", type=int, default=3)
+    p.add_argument("--steps", type=int, default=3, help="timed steps")
     p.add_argument("--warmup", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure everything beside the headline figure: the "
+                        "single-layer / Gram roofline extras, the transfer-inclusive step, the 8-rank shard "
+                        "projection, the decoder flow, the other configs and the CPU baselines (each can be "
+                        "switched off by its --no-* flag); without --full none of them runs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last timed step returned (ternary codes, "
+                        "alpha, mu, perm of every linear; a fixed seeded sample of rows where the whole "
+                        "would pass 64 MB) as DIR/<name>.npy in float32 (dump_outputs)")
     p.add_argument("--workload", choices=["model", "layer", "split", "decoder"], default="model",
                    help="model: LPT-sharded 7B step; layer: one layer per rank (weak); split: one n x m "
                         "layer, its Gram data-parallel over the ranks (strong)")
@@ -1072,6 +1086,62 @@ class DryStep:
         return res
 
 
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all files together stay under 64 MB
+
+
+def step_results(workload, out):
+    """What one timed step returned, as {linear name: (codes, alpha, mu, perm)} with `codes` a
+    function giving the int8 n x m ternary codes: the model step's {unit.linear: {T2 | T, alpha, mu,
+    perm}} (2-bit packed codes are unpacked on the device), the layer step's LayerOutput, the
+    split step's list of them (rank 0)."""
+    if workload == "model":
+        res = {}
+        for name, e in out.items():
+            n, m = e["alpha"].shape[0], e["perm"].numel()
+            res[name] = ((lambda e=e: e["T"]) if "T" in e else
+                         (lambda e=e, n=n, m=m: pt2q.engine.unpack_ternary(e["T2"], (n, m))),
+                         e["alpha"], e["mu"], e["perm"])
+        return res
+    outs = out if isinstance(out, (list, tuple)) else [out]
+    return {f"layer{i}": (lambda o=o: o.T, o.alpha, o.mu, o.perm) for i, o in enumerate(outs)}
+
+
+def dump_outputs(path, workload, out):
+    """--dump-outputs: the last timed step's results as float32 arrays T.npy (ternary codes),
+    alpha.npy, mu.npy, perm.npy under `path`, each the linears' values back to back in sorted name
+    order.  Every permutation is written whole.  Of the row-shaped results every row is written
+    while all four files fit DUMP_BUDGET_BYTES; past that (a 7B step holds 6.5e9 codes) a fixed
+    sample of rows per linear, the same rows in every run: RandomState(crc32(name)).permutation(n),
+    its first R_T rows for the codes and its first R_A for alpha and mu, half the budget each."""
+    import zlib
+    res = step_results(workload, out)
+    names = sorted(res)
+    dims = {k: (res[k][1].shape[0], res[k][3].numel(), res[k][1].shape[1]) for k in names}  # n, m, blocks
+    left = DUMP_BUDGET_BYTES - 4 * sum(m for _, m, _ in dims.values())
+    if 4 * sum(n * (m + 2 * B) for n, m, B in dims.values()) <= left:
+        rt = ra = max(n for n, _, _ in dims.values())
+    else:
+        rt = max(1, left // 2 // (4 * sum(m for _, m, _ in dims.values())))
+        ra = max(1, left // 2 // (8 * sum(B for _, _, B in dims.values())))
+    parts = {"T": [], "alpha": [], "mu": [], "perm": []}
+    for k in names:
+        codes, alpha, mu, perm = res[k]
+        n = dims[k][0]
+        order = np.random.RandomState(zlib.crc32(k.encode())).permutation(n)
+        pick = lambda r: slice(None) if r >= n else torch.from_numpy(np.sort(order[:r])).to(alpha.device)  # noqa: E731
+        parts["T"].append(codes()[pick(rt)].float().cpu().numpy().ravel())
+        parts["alpha"].append(alpha[pick(ra)].float().cpu().numpy().ravel())
+        parts["mu"].append(mu[pick(ra)].float().cpu().numpy().ravel())
+        parts["perm"].append(perm.float().cpu().numpy().ravel())
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for k, v in parts.items():
+        arr = np.concatenate(v).astype(np.float32)
+        np.save(os.path.join(path, k + ".npy"), arr)
+        total += arr.nbytes
+    return {"dir": path, "linears": len(names), "bytes": total, "rows_T": rt, "rows_alpha_mu": ra}
+
+
 def shard_main(a, dev, io):
     """bench.py --gpus N --shard r|all (one process, one GPU): rank r's LPT shard of an N-rank
     model step timed alone ('all': the whole step on this GPU first -- T1 and its phases -- then
@@ -1110,6 +1180,11 @@ def shard_main(a, dev, io):
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     a = parse(argv)
+    if not a.full:  # a plain run: set up, warm up, time the steps, dump, print the line
+        a.no_extra = a.no_cpu_baseline = True
+    if a.dump_outputs and (a.shard is not None or a.workload == "decoder"):
+        print("[bench] refusing: --dump-outputs covers the model, layer and split workloads", file=sys.stderr)
+        return 2
     rc = launch_or_check(a, argv)
     if rc is not None:
         return rc
@@ -1172,9 +1247,11 @@ def main(argv=None):
     with no_gc():
         t0 = time.perf_counter()
         step_ms = []
+        last = None
         for i in range(a.steps):
             ts = time.perf_counter()
-            work.step()
+            last = None  # the previous step's results go before the next step allocates its own
+            last = work.step()
             sync()  # per-step wall (box-to-box and step-to-step spread); the step ends in host reads anyway
             step_ms.append(1e3 * (time.perf_counter() - ts))
             if a.steps > 3:
@@ -1224,6 +1301,11 @@ def main(argv=None):
                    "model": "sharding.unit_cost (per-unit shares of the fitted phase model), LPT over the ranks; "
                             "sharding.shard_cost: the phase model of each rank's step"}
     log(rank, f"timed {a.steps} steps: {ms_per_step:.1f} ms/step")
+    dumped = None
+    if a.dump_outputs and rank == 0 and last is not None:  # rank 0 holds the gathered results
+        dumped = dump_outputs(a.dump_outputs, a.workload, last)
+        log(rank, f"outputs of the last timed step: {dumped}")
+    last = None
     if a.dry_run:
         if rank == 0:
             got = work.last
@@ -1234,6 +1316,8 @@ def main(argv=None):
                    "data": "dry run (no kernels)", "ranks": ranks, "lpt_balance": balance,
                    "gathered_linears": sorted(got) if got is not None else None,
                    "config": {"workload": "dry run", "weight_columns_per_step": cols}}
+            if dumped is not None:
+                res["dumped_outputs"] = dumped
             print(json.dumps(res), flush=True)
         if world > 1:
             dist.destroy_process_group()
@@ -1378,6 +1462,8 @@ def main(argv=None):
             res["ranks"] = ranks
             res["lpt_balance"] = balance
             res["gathered_linears"] = getattr(work, "gathered", None)
+        if dumped is not None:
+            res["dumped_outputs"] = dumped
         if roof is not None:
             res["roofline"] = roof
         if (a.workload == "model" and world == 1 and not a.no_extra and not a.no_h2d and work.gf is not None

@@ -75,6 +75,100 @@ def test_shards_union_equals_whole_step():
             assert torch.equal(got[k][f], r[f]), (k, f)
 
 
+def test_dump_outputs_equals_step_results(tmp_path, monkeypatch):
+    """bench.dump_outputs: the four float32 files hold exactly the step's results (codes unpacked
+    from the 2-bit packing), linear after linear in sorted name order; with a budget too small for
+    every row, the same fixed rows of every linear on each call, and no more bytes than the budget."""
+    import numpy as np
+    bench, ms = _small_step()
+    res = ms.step()
+    torch.cuda.synchronize()
+    info = bench.dump_outputs(str(tmp_path / "all"), "model", res)
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("T", "alpha", "mu", "perm")}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert info["linears"] == 14 and info["bytes"] == sum(v.nbytes for v in got.values())
+    want = {k: [] for k in got}
+    for name in sorted(res):
+        e = res[name]
+        n, m = e["alpha"].shape[0], e["perm"].numel()
+        want["T"].append(bench.pt2q.engine.unpack_ternary(e["T2"], (n, m)).float().cpu().numpy().ravel())
+        for k in ("alpha", "mu", "perm"):
+            want[k].append(e[k].float().cpu().numpy().ravel())
+    for k in got:
+        assert np.array_equal(got[k], np.concatenate(want[k])), k
+    assert set(np.unique(got["T"])) == {-1.0, 0.0, 1.0}
+    # a sampled dump: 1/8 of the whole
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", info["bytes"] // 8)
+    a = bench.dump_outputs(str(tmp_path / "s1"), "model", res)
+    b = bench.dump_outputs(str(tmp_path / "s2"), "model", res)
+    assert a["bytes"] == b["bytes"] <= info["bytes"] // 8 and a["rows_T"] >= 1
+    for k in got:
+        s1, s2 = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.npy")
+        assert np.array_equal(s1, s2), k
+    assert np.array_equal(np.load(tmp_path / "s1" / "perm.npy"), got["perm"])
+    # the sample's rows are rows of the whole: the first linear's first sampled row of codes
+    name = sorted(res)[0]
+    n, m = res[name]["alpha"].shape[0], res[name]["perm"].numel()
+    row = np.load(tmp_path / "s1" / "T.npy")[:m]
+    assert any(np.array_equal(row, r) for r in got["T"][:n * m].reshape(n, m))
+
+
+def test_dump_outputs_layer_workload(tmp_path):
+    """--workload layer: the dump holds the replayed layer's LayerOutput."""
+    import numpy as np
+    import bench
+    a = bench.parse(["--workload", "layer", "--n", "512", "--m", "512", "--tokens", "2048"])
+    bench._load_runtime(False)
+    bench.resolve(a)
+    out = bench.LayerStep(a, 0, 1, torch.device("cuda", 0), torch.float16).step()
+    torch.cuda.synchronize()
+    bench.dump_outputs(str(tmp_path), "layer", out)
+    for k in ("T", "alpha", "mu", "perm"):
+        want = getattr(out, k).float().cpu().numpy().ravel()
+        assert np.array_equal(np.load(tmp_path / f"{k}.npy"), want) and want.size > 0, k
+
+
+def _run_bench(args, timeout):
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--layers", "2",
+                        "--hidden", "512", "--inter", "768", "--tokens", "2048"] + args,
+                       capture_output=True, text=True, timeout=timeout, env=env, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0]), p.stderr
+
+
+def test_plain_run_line_and_dump(tmp_path):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` run: exactly N timed steps, the headline
+    fields, nothing of what --full measures; --dump-outputs writes the same bytes on a second run."""
+    import numpy as np
+    d, err = _run_bench(["--steps", "4", "--warmup", "1", "--dump-outputs", str(tmp_path / "a")], 120)
+    assert d["steps"] == 4 and err.count("[bench] step ") == 4
+    assert d["metric"] == "weight-columns quantized/sec (and s/layer) at d=4096" and d["unit"] == "cols/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "fp16->f32" and d["ms_per_step"] > 0
+    assert abs(d["value"] - d["config"]["weight_columns_per_step"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert "roofline" not in d and "cpu_baseline" not in d and d["extra"] == {}
+    assert "cpu baseline" not in err and "h2d" not in err
+    d2, _ = _run_bench(["--steps", "1", "--warmup", "1", "--dump-outputs", str(tmp_path / "b")], 120)
+    assert d2["steps"] == 1
+    for k in ("T", "alpha", "mu", "perm"):
+        x, y = np.load(tmp_path / "a" / f"{k}.npy"), np.load(tmp_path / "b" / f"{k}.npy")
+        assert x.dtype == np.float32 and x.size > 0 and np.array_equal(x, y), k
+
+
+def test_full_run_line():
+    """`--full` keeps everything the line carried beside the headline: the Gram roofline with the
+    live stage rooflines, the single-layer extras, the transfer-inclusive step, the CPU baselines."""
+    d, err = _run_bench(["--steps", "1", "--warmup", "1", "--full"], 240)
+    assert d["ms_per_step"] > 0 and d["steps"] == 1
+    assert d["roofline"]["frac"] > 0 and d["roofline"]["stages"]["dominant"]["busy_s"] > 0
+    assert d["extra"]["s_per_layer_d4096"] > 0 and d["extra"]["h2d"]["ms_per_step"] > 0
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["one_core"]["value"] > 0
+
+
 def test_shard_mode_line():
     """`bench.py --gpus 2 --shard all` (one process): the whole step, then both shards, one JSON
     line with the projection fields."""

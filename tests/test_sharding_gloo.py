@@ -365,6 +365,40 @@ def test_bench_refuses_gpus_world_size_mismatch():
     assert p.returncode == 2 and "refusing" in p.stderr
 
 
+def test_bench_dump_outputs_dry_run(tmp_path):
+    """`bench.py --dump-outputs DIR` (--dry-run: the stub units' results): T / alpha / mu / perm of
+    the last timed step as float32 .npy, every linear back to back in sorted name order, and the
+    same bytes from a second run with the same arguments; the line keeps its headline fields."""
+    import subprocess
+    import sys
+
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    args = ["--gpus", "1", "--layers", "2", "--hidden", "64", "--inter", "96", "--tokens", "256",
+            "--steps", "2", "--warmup", "1", "--dry-run"]
+    runs = []
+    for d in ("a", "b"):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args +
+                           ["--dump-outputs", str(tmp_path / d)],
+                           capture_output=True, text=True, timeout=120, env=env, cwd=ROOT)
+        assert p.returncode == 0, p.stderr[-3000:]
+        line = _last_json(p.stdout)
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["T.npy", "alpha.npy", "mu.npy", "perm.npy"]
+        runs.append({k: np.load(tmp_path / d / f"{k}.npy") for k in ("T", "alpha", "mu", "perm")})
+        assert all(v.dtype == np.float32 and v.ndim == 1 for v in runs[-1].values())
+        assert line["dumped_outputs"]["bytes"] == sum(v.nbytes for v in runs[-1].values()) <= 64e6
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), k
+    # the stub gives 8 rows per linear, block 128 (one block at these widths): 14 linears, all rows
+    sh = _sharding()
+    units = sh.llama_units(2, 64, 96, 256)
+    ms = [m for _, lins, _ in units for _, _, m in lins]
+    assert runs[0]["perm"].size == sum(ms) and runs[0]["T"].size == 8 * sum(ms)
+    assert runs[0]["alpha"].size == runs[0]["mu"].size == 8 * len(ms)
+    assert set(np.unique(runs[0]["T"])) <= {-1.0, 0.0, 1.0}
+
+
 # ----------------------------------------------------------------- GramsFirst stall reporting
 
 def test_grams_first_keeps_an_early_stall():
