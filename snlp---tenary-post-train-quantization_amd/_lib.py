@@ -15,7 +15,7 @@ PT2Q_OK = 0
 PT2Q_E_NOT_SPD = 2
 PT2Q_E_STALL = 6
 STATUS_BYTES = 256  # the status word at the head of a workspace (include/pt2q.h)
-STALL_BITS = {0x1: "Gram partial-tile hand-off", 0x2: "ATQ S1/d hand-off", 0x4: "top-k pick hand-off"}
+STALL_BITS = {0x1: "Gram partial-tile hand-off", 0x2: "ATQ S1/d hand-off"}
 F32, F16, BF16, I8 = 0, 1, 2, 3
 FLAG_SSR = 0x1
 FLAG_S1_GIVEN = 0x2

@@ -13,79 +13,28 @@
 
 namespace {
 
-// Tuning, read once at library load -- see Pt2qTuning.  Release builds read only the debug
-// spin cap; every kernel-selecting variable is a development-build (PT2Q_DEV_PROBES) override.
-Pt2qTuning load_tuning() {
-  Pt2qTuning t;
-#ifdef PT2Q_DEV_PROBES
-  auto geti = [](const char* k, int& v) {
-    if (const char* e = std::getenv(k)) v = std::atoi(e);
-  };
-  auto getb = [](const char* k, bool& v) {
-    if (const char* e = std::getenv(k)) v = e[0] != '0';
-  };
-  // Kernel-selecting overrides and knock-outs: read only by a development build (make
-  // DEV_PROBES=1, tools/build_dev_lib.sh).  The release library runs the defaults of Pt2qTuning
-  // whatever the environment holds, so no variable can switch it onto a kernel variant the GPU
-  // tests do not cover (or onto a knock-out whose results are garbage).
-  geti("PT2Q_GRAM_SUPER", t.gram_super);
-  geti("PT2Q_GRAM_GROUPS", t.gram_groups);
-  geti("PT2Q_GRAM_CUS", t.gram_cus);
-  getb("PT2Q_GRAM_STREAMK", t.gram_split);
-  getb("PT2Q_GRAM_PAIR", t.gram_pair);
-  getb("PT2Q_GRAM_DP", t.gram_dp);
-  getb("PT2Q_GRAM_WIDE", t.gram_wide);
-  geti("PT2Q_GRAM_SEGLEN", t.gram_seglen);
-  geti("PT2Q_GEMM_TILE", t.gemm_tile);
-  getb("PT2Q_RANK_UPDATE", t.rank_update);
-  geti("PT2Q_CHOL_PANEL", t.chol_panel);
-  geti("PT2Q_CHOL_SUBPANEL", t.chol_subpanel);
-  getb("PT2Q_CHOL_LOOKAHEAD", t.chol_lookahead);
-  getb("PT2Q_WBAR_FUSED", t.wbar_fused);
-  getb("PT2Q_SIM_SPLIT", t.sim_split);
-  getb("PT2Q_EF_WBAR", t.ef_wbar);
-  geti("PT2Q_GEMMX_STAGES", t.gemmx_stages);
-  getb("PT2Q_GEMMX_GRAM", t.gemmx_gram);
-  getb("PT2Q_CHOL_LANE", t.chol_lane);
-  getb("PT2Q_S1_IN_ATQ", t.s1_in_atq);
-  getb("PT2Q_EF_GEMM", t.ef_kernel);
-  geti("PT2Q_WIDE_WAVES", t.wide_waves);
-  geti("PT2Q_ATQ_OCC", t.atq_occ);
-  getb("PT2Q_ATQ_VEC", t.atq_vec);
-  getb("PT2Q_GRAM_ORDER", t.gram_order);
-  getb("PT2Q_ATQ_PC", t.atq_pc);
-  getb("PT2Q_ATQ_PC_REGS", t.atq_pc_regs);
-  geti("PT2Q_EF_V2", t.ef_v2);
-  // knock-outs (tools/ef2_knock.sh, tools/atq_knock.sh; results garbage)
-  geti("PT2Q_EF2_PROBE", t.ef2_probe);
-  geti("PT2Q_ATQ_PROBE", t.atq_probe);
-  geti("PT2Q_EF2_STAGGER", t.ef2_stagger);
-  geti("PT2Q_EF2_PER_CU", t.ef2_per_cu);
-  geti("PT2Q_EF2_TEAMS", t.ef2_teams);
-  geti("PT2Q_EF2_TEAM_OFFSET", t.ef2_team_offset);
-  getb("PT2Q_EF2_G1LDS", t.ef2_g1lds);
-  if (t.ef2_per_cu != 1) t.ef2_per_cu = 2;
-  if (t.wide_waves != 8) t.wide_waves = 4;
-  if (t.atq_occ != 0) t.atq_occ = 6;
-#endif
-  // release and development: the stall-reporting test hook (tests/test_gpu_status.py)
+// The spin caps, read once at library load -- see Pt2qSpinCaps.  PT2Q_DEBUG_SPIN_CAP, the
+// stall-reporting test hook (tests/test_gpu_status.py), is the only environment variable the
+// library reads; every kernel choice is fixed in the code.
+Pt2qSpinCaps load_spin_caps() {
+  Pt2qSpinCaps t;
   if (const char* e = std::getenv("PT2Q_DEBUG_SPIN_CAP")) {
     const long c = std::atol(e);
-    if (c >= 0) t.spin_cap_long = t.spin_cap_short = t.spin_cap_fallback = c;
+    if (c >= 0) t.spin_cap_long = t.spin_cap_fallback = c;
   }
   return t;
 }
 
 }  // namespace
 
-const Pt2qTuning& pt2q_tuning() {
-  static const Pt2qTuning t = load_tuning();
+const Pt2qSpinCaps& pt2q_spin_caps() {
+  static const Pt2qSpinCaps t = load_spin_caps();
   return t;
 }
 
 namespace {
 
-const Pt2qTuning& g_tuning_at_load = pt2q_tuning();  // forces the read at dlopen
+const Pt2qSpinCaps& g_spin_caps_at_load = pt2q_spin_caps();  // forces the read at dlopen
 
 struct Carve {
   char* p;
@@ -176,11 +125,9 @@ struct BlockWs {
 };
 
 // Whether the error feedback may hand the next block's SSR its w-bar partials (ef.hip / ssr.hip
-// pre path: the fused w-bar launch's conditions; PT2Q_EF_WBAR=0 keeps the separate pass).
+// pre path: the fused w-bar launch's conditions).
 inline bool ef_wbar_ok(int n, long ldw, const float* Wt) {
-  const Pt2qTuning& t = pt2q_tuning();
-  return t.ef_wbar && t.wbar_fused && t.ef_kernel && n <= 16384 && n % 4 == 0 && ldw % 4 == 0 &&
-         (uintptr_t)Wt % 16 == 0;
+  return n <= 16384 && n % 4 == 0 && ldw % 4 == 0 && (uintptr_t)Wt % 16 == 0;
 }
 
 // variant G's AGA matrix for blocks wider than one workgroup's LDS holds (> 128 columns)
@@ -204,7 +151,7 @@ bool carve_blocks(Carve& c, int n, int m, int b, BlockWs& w, int flags = 0) {
   w.rem[0] = c.take<int>((size_t)m);
   w.rem[1] = c.take<int>((size_t)m);
   w.blk = c.take<int>((size_t)bb);
-  // [2k, 2k+1] ATQ; [2B+2k, 2B+2k+1] top-k/S1 sync; [4B ..) the wbar hand-off counters
+  // [2k, 2k+1] ATQ; [2B+2k, 2B+2k+1] the ATQ launch's S1 sync; [4B ..) the wbar hand-off counters
   w.counters = c.take<int>((size_t)4 * B + pt2q_ssr_counter_ints(n));
   w.iters = c.take<int>((size_t)B);
   w.iters_part = c.take<int>((size_t)ceil_div(n, 16) * 4);  // one per ATQ wave (4 waves of 4 rows per workgroup)
@@ -334,17 +281,14 @@ int run_blocks(const void* W, int wdtype, long ldw_in, int n, int m, int b, int 
     int* nrem = w.rem[cur ^ 1];
     // variant M with blocks <= 128: the ATQ launch also forms S1/d (no separate launch; off
     // the critical path of the rows, which need it only for their AGA)
-    const bool s1_in_atq = aga == PT2Q_AGA_ACT && bs <= 128 && pt2q_tuning().s1_in_atq;
-    const bool s1_in_topk = !s1_in_atq && ssr && r > b && aga == PT2Q_AGA_ACT && bs <= 128;
+    const bool s1_in_atq = aga == PT2Q_AGA_ACT && bs <= 128;
     StageScope ts_ssr(PT2Q_TIMER_SSR, st);
     if (ssr) {
       if (r > b) {
         if ((rc = pt2q_launch_ssr_similarity(w.Wt, w.ldw, n, rem, r, part, wn, sim, st, w.counters + 4 * B,
                                              nullptr, pre)) != PT2Q_OK)
           return rc;
-        if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm + processed, st,
-                                       s1_in_topk ? A : nullptr, lda, w.S1, w.d,
-                                       w.counters + 2 * B + 2 * k, w.status)) != PT2Q_OK)
+        if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm + processed, st)) != PT2Q_OK)
           return rc;
       } else {
         if ((rc = pt2q_launch_select_seq(1, 0, bs, m, rem, w.blk, nrem, perm + processed, st)) != PT2Q_OK)
@@ -360,7 +304,7 @@ int run_blocks(const void* W, int wdtype, long ldw_in, int n, int m, int b, int 
     if (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_HESS) {
       if (hess_wide(flags, bs)) {
         if ((rc = hess_block_s1(A, lda, w.blk, bs, w, st)) != PT2Q_OK) return rc;
-      } else if (!s1_in_topk && !s1_in_atq &&
+      } else if (!s1_in_atq &&
                  (rc = pt2q_launch_aga_s1(aga == PT2Q_AGA_ACT ? 1 : 2, A, lda, w.blk, bs, w.S1, w.d, st)) != PT2Q_OK) {
         return rc;
       }
@@ -376,9 +320,8 @@ int run_blocks(const void* W, int wdtype, long ldw_in, int n, int m, int b, int 
     ts_atq.close();
     StageScope ts_ef(PT2Q_TIMER_EF, st);
     const bool want = ssr && nr > b && ef_wbar_ok(n, w.ldw, w.Wt);  // the next block runs SSR over nrem
-    rc = (nr > 0 && pt2q_tuning().ef_kernel)
-             ? pt2q_launch_ef(w.Ck, m, w.Et, w.Wt, w.ldw, m, nrem, nr, bs, st, nullptr, want ? part : nullptr, n)
-             : PT2Q_E_UNSUPPORTED;
+    rc = nr > 0 ? pt2q_launch_ef(w.Ck, m, w.Et, w.Wt, w.ldw, m, nrem, nr, bs, st, nullptr, want ? part : nullptr, n)
+                : PT2Q_E_UNSUPPORTED;
     if (rc != PT2Q_OK && rc != PT2Q_E_UNSUPPORTED) return rc;
     pre = want && rc == PT2Q_OK;
     if (nr > 0 && rc == PT2Q_E_UNSUPPORTED) {
@@ -463,8 +406,7 @@ int run_blocks_group(int count, const void* const* W, int wdtype, long ldw_in, i
       if ((rc = pt2q_launch_ssr_similarity(w.Wt, w.ldw, n, rem, r, part, wn, sim, st, w.counters + 4 * B, &g,
                                            pre)) != PT2Q_OK)
         return rc;
-      if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm64 + processed, st, nullptr, 0, nullptr,
-                                     nullptr, nullptr, w.status, &g)) != PT2Q_OK)
+      if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm64 + processed, st, &g)) != PT2Q_OK)
         return rc;
     } else if ((rc = pt2q_launch_select_seq(ssr ? 1 : 0, ssr ? 0 : processed, bs, m, ssr ? rem : nullptr, w.blk,
                                             nrem, perm64 + processed, st, &g)) != PT2Q_OK) {
@@ -508,14 +450,13 @@ int run_blocks_group(int count, const void* const* W, int wdtype, long ldw_in, i
 bool dtype_ok(int dt) { return dt == PT2Q_F32 || dt == PT2Q_F16 || dt == PT2Q_BF16; }
 
 // Every condition under which pt2q_quantize_blocks_group runs (else PT2Q_E_UNSUPPORTED): blocks
-// of <= 128 columns with b < m, variant M or no AGA, the tuning defaults (S1 in the ATQ launch,
-// the EF kernel, the fused w-bar), n <= 16384 with n % 4 == 0, and the error feedback's own
+// of <= 128 columns with b < m, variant M (S1 in the ATQ launch) or no AGA, the fused w-bar's
+// n <= 16384 with n % 4 == 0, and the error feedback's own
 // limits (pt2q_launch_ef: coefficient rows 16-byte aligned, every Wt under 2 GiB of buffer range).
 bool group_ok(int n, int m, int b, int flags) {
   const int aga = flags & PT2Q_AGA_MASK;
-  const Pt2qTuning& tu = pt2q_tuning();
   return n > 0 && m > 0 && b > 0 && b <= 128 && b < m && m < 65536 &&
-         (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_NONE) && tu.s1_in_atq && tu.ef_kernel && tu.wbar_fused &&
+         (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_NONE) &&
          n <= 16384 && n % 4 == 0 && m % 4 == 0 && (long)m * round_up(n, 64) * 4 < 0x80000000L;
 }
 
@@ -968,8 +909,7 @@ extern "C" int pt2q_error_feedback(float* W, int64_t ldw, int n, int m, const in
   // C[k][e] = Hinv[blk_k][rem_e] / clamp(Hinv[blk_k][blk_k], 1e-8)   (main.py:201-209)
   if ((rc = pt2q_launch_ef_coeffs(Hinv, ldhi, blk32, bs, rem32, r, Ck, ldc, st)) != PT2Q_OK) return rc;
   // W[:, rem] -= E @ C   (main.py:214: product rounded, then one subtraction)
-  rc = pt2q_tuning().ef_kernel ? pt2q_launch_ef(Ck, ldc, Et, Wt, ldW, m, rem32, r, bs, st)
-                               : PT2Q_E_UNSUPPORTED;
+  rc = pt2q_launch_ef(Ck, ldc, Et, Wt, ldW, m, rem32, r, bs, st);
   if (rc == PT2Q_E_UNSUPPORTED) {
     GemmDesc g{};
     g.M = r; g.N = n; g.K = bs;

@@ -16,6 +16,7 @@
 
 #include "common.hpp"
 #include "internal.hpp"
+#include "probe.hpp"
 
 namespace {
 
@@ -198,7 +199,6 @@ struct BlockArgs {
   float* dw;
   int* status;       // stall reports (nullable)
   long cap;          // polls before a wait gives up
-  int probe;         // development knock-outs (pt2q_tuning().atq_probe; 0 in release builds)
 };
 
 // Grouped launch: linear z's pointers -- its workspace slice, its raw Gram.
@@ -304,8 +304,8 @@ PT2Q_DEV int block_rows(const BlockArgs& A, int row0, bool skip_itf, bool count_
   bool zero = row_init(R, wsum, &a, &m);
   if (count_zero && valid && l == 0 && zero) atomicAdd(&A.counters[0], 1);
   int it = 0;
-  if (!skip_itf && !(A.probe & 4)) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
-  if (A.S1 && A.nS1 > 0 && !(A.probe & 1)) {  // S1 / d from this launch's leading workgroups (write-through)
+  if (!skip_itf && !probe::atq_no_itf) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
+  if (A.S1 && A.nS1 > 0 && !probe::atq_no_s1_wait) {  // S1 / d from this launch's leading workgroups (write-through)
     int ready = 1;
     if ((threadIdx.x & 63) == 0) ready = wait_flag_ge<2>(&A.s1sync[0], 1, A.cap, nullptr, 0);
     ready = __builtin_amdgcn_readfirstlane(ready);
@@ -340,8 +340,8 @@ PT2Q_DEV int block_rows(const BlockArgs& A, int row0, bool skip_itf, bool count_
 
 // RG row groups per wave (rows base + 16 g + r, g < RG): every group's gathers are issued before
 // the first group's arithmetic, the block indices and S1 / d are loaded once for all of them.  The
-// block ATQ is bound by these load round trips, not by its ITF arithmetic (knock-outs,
-// tools/atq_knock.sh: skipping ITF altogether moved a grouped 7B launch 100 -> 99 us), so one
+// block ATQ is bound by these load round trips, not by its ITF arithmetic (knock-out build
+// -DPT2Q_ATQ_KPROBE=4: skipping ITF altogether moved a grouped 7B launch 100 -> 99 us), so one
 // wave carrying several groups' loads at once is what shortens it.  Per row, the values and their
 // order are block_rows' (same Row arithmetic), so the bits are the same.
 template <int NS, bool F, int RG>
@@ -361,7 +361,7 @@ PT2Q_DEV int block_rows_rg(const BlockArgs& A, int base) {
     const int ic = i < A.n ? i : 0;
 #pragma unroll
     for (int s = 0; s < NS; ++s)
-      v[g][s] = (A.probe & 32) ? (float)(ic + s) : A.Wt[(long)colrow[s] * A.ldw + ic];
+      v[g][s] = probe::atq_no_gather ? (float)(ic + s) : A.Wt[(long)colrow[s] * A.ldw + ic];
   }
   const bool s1_now = A.S1 && A.nS1 == 0;
   float S1[NS];
@@ -387,9 +387,9 @@ PT2Q_DEV int block_rows_rg(const BlockArgs& A, int base) {
     const bool zero = row_init(R, wsum, &a, &m);
     if (valid && l == 0 && zero) atomicAdd(&A.counters[0], 1);
     int it = 0;
-    if (!(A.probe & 4)) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
+    if (!probe::atq_no_itf) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
     itmax = max(itmax, it);
-    if (g == 0 && A.S1 && A.nS1 > 0 && !(A.probe & 1)) {  // S1 / d from the leading workgroups, once
+    if (g == 0 && A.S1 && A.nS1 > 0 && !probe::atq_no_s1_wait) {  // S1 / d from the leading workgroups, once
       int ready = 1;
       if (lane == 0) ready = wait_flag_ge<2>(&A.s1sync[0], 1, A.cap, nullptr, 0);
       ready = __builtin_amdgcn_readfirstlane(ready);
@@ -408,7 +408,7 @@ PT2Q_DEV int block_rows_rg(const BlockArgs& A, int base) {
     }
     if (A.S1) row_aga(R, S1, dv, &a, &m);
     if (valid) {
-      if (l == 0 && !(A.probe & 256)) {
+      if (l == 0 && !probe::atq_no_scales) {
         A.alpha[i] = a;
         A.mu[i] = m;
       }
@@ -416,8 +416,13 @@ PT2Q_DEV int block_rows_rg(const BlockArgs& A, int base) {
       for (int s = 0; s < NS; ++s)
         if (R.has(s)) {
           const int k = l + 16 * s;
-          if (!(A.probe & 8)) A.Tt[(long)colrow[s] * A.ldt + i] = (int8_t)R.t[s];
-          if (A.Et && !(A.probe & 128)) A.Et[(long)k * A.lde + i] = R.w[s] - (a * R.t[s] + m);
+          // (the row index re-read as a fresh 32-bit value: sharing the gathers' 64-bit extension
+          // of it would keep NS more registers live across the row arithmetic -- 158 -> 175 VGPRs
+          // and one wave per SIMD less at NS = 16)
+          int cr = colrow[s];
+          asm volatile("" : "+v"(cr));
+          if (!probe::atq_no_codes) A.Tt[(long)cr * A.ldt + i] = (int8_t)R.t[s];
+          if (A.Et && !probe::atq_no_et) A.Et[(long)k * A.lde + i] = R.w[s] - (a * R.t[s] + m);
         }
     }
   }
@@ -428,7 +433,7 @@ PT2Q_DEV int block_rows_rg(const BlockArgs& A, int base) {
 // groups of 4) and moves them as 16-byte pieces -- a block column's 16 rows of W are read, and its
 // 16 codes and 16 error terms written, 16 bytes per lane.  The per-element form (block_rows_rg:
 // 4- and 1-byte pieces, 16 cache lines per instruction) spent ~18 us of a grouped 7B launch on the
-// code stores and ~18 us on the error-term stores (knock-outs, tools/atq_knock.sh masks 8 / 128).
+// code stores and ~18 us on the error-term stores (knock-outs, PT2Q_ATQ_KPROBE masks 8 / 128).
 // Per row, the arithmetic is block_rows_rg's, so the bits are the same.
 constexpr int VEC_KC = 32;                  // block columns per staging chunk
 constexpr int VEC_KS = 20;                  // floats per staged column: 16 rows + pad (16-B aligned,
@@ -448,14 +453,18 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
   const int r = lane >> 4, l = lane & 15;
   const int q4 = lane >> 2, part = lane & 3;  // staging lanes: chunk columns q4 + 16 h, rows 4 part ..
   if (base >= A.n) return 0;                  // n % 16 == 0: a wave's rows are all valid or none
-  // W: every chunk's 16-byte pieces in flight, then through the stage into the row layout
+  // W: every chunk's 16-byte pieces, then through the stage into the row layout.  The pieces are
+  // paced: a piece is fetched once its block index and the piece before it have landed.  All
+  // eight in flight at once measured slower, 52.2 against 51.1 us per launch of a grouped 7B
+  // block (profiles/knob_removal_atq_gather_pacing.txt), so the wait is written out here.
   float4 gv[NC][2];
 #pragma unroll
   for (int c = 0; c < NC; ++c)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const long col = A.blk[VEC_KC * c + q4 + 16 * h];
-      gv[c][h] = (A.probe & 32) ? make_float4(0.f, 1.f, 2.f, 3.f)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      gv[c][h] = probe::atq_no_gather ? make_float4(0.f, 1.f, 2.f, 3.f)
                                 : *(const float4*)(A.Wt + col * A.ldw + base + 4 * part);
     }
   const bool s1_now = A.S1 && A.nS1 == 0;
@@ -490,9 +499,9 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
     const bool zero = row_init(R, wsum, &a, &m);
     if (l == 0 && zero) atomicAdd(&A.counters[0], 1);
     int it = 0;
-    if (!(A.probe & 4)) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
+    if (!probe::atq_no_itf) it = row_itf<true>(R, wsum, A.max_iter, &a, &m);
     itmax = max(itmax, it);
-    if (g == 0 && A.S1 && A.nS1 > 0 && !(A.probe & 1)) {  // S1 / d from the leading workgroups, once
+    if (g == 0 && A.S1 && A.nS1 > 0 && !probe::atq_no_s1_wait) {  // S1 / d from the leading workgroups, once
       int ready = 1;
       if (lane == 0) ready = wait_flag_ge<2>(&A.s1sync[0], 1, A.cap, nullptr, 0);
       ready = __builtin_amdgcn_readfirstlane(ready);
@@ -507,7 +516,7 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
       }
     }
     if (A.S1) row_aga(R, S1, dv, &a, &m);
-    if (l == 0 && !(A.probe & 256)) {
+    if (l == 0 && !probe::atq_no_scales) {
       A.alpha[i] = a;
       A.mu[i] = m;
     }
@@ -526,7 +535,7 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
   // column q + 64 h (16 bytes, row-group-major) and transposes it to row order
 #pragma unroll
   for (int s = 0; s < NS; ++s) stg32[4 * (l + 16 * s) + r] = tc[s];
-  if (!(A.probe & 8)) {
+  if (!probe::atq_no_codes) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int k = lane + 64 * h;
@@ -541,7 +550,7 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
   }
   asm volatile("" ::: "memory");  // code loads of the stage before its float reuse (see above)
   // error terms, a chunk of 32 columns at a time
-  if (A.Et && !(A.probe & 128)) {
+  if (A.Et && !probe::atq_no_et) {
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
 #pragma unroll
@@ -560,7 +569,7 @@ PT2Q_DEV int block_rows_vec(const BlockArgs& A, int base) {
 }
 
 // row groups per wave of the fused block ATQ (registers: RG x NS gathered values in flight): 4 at
-// 128-column blocks (122 VGPRs, four waves per SIMD), 2 in the six-wave variant (PT2Q_ATQ_OCC),
+// 128-column blocks (122 VGPRs, four waves per SIMD), 2 in the six-wave variant (OCC = 6),
 // one group for wider blocks
 template <int NS, int OCC>
 constexpr int atq_rg() { return NS == 8 ? (OCC > 0 ? 2 : 4) : 1; }
@@ -669,7 +678,7 @@ template <int NS, bool F, int RG, bool VEC>
 PT2Q_DEV void atq_block_body(const BlockArgs& A0, const Grp& g, CoeffArgs K, int rowgrid, int cgrid);
 
 // OCC: 0 = the compiler's register budget (four waves per SIMD at NS = 8); 6 = at least six waves
-// per SIMD (80 VGPRs, two row groups per wave, no spills: PT2Q_ATQ_OCC).  VEC: block_rows_vec.
+// per SIMD (80 VGPRs, two row groups per wave, no spills).  VEC: block_rows_vec.
 template <int NS, bool F, int OCC, bool VEC = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1, 8))) void atq_block_kernel(
     BlockArgs A0, Grp g, CoeffArgs K, int rowgrid, int cgrid) {
@@ -688,7 +697,7 @@ PT2Q_DEV void atq_block_body(const BlockArgs& A0, const Grp& g, CoeffArgs K, int
   int b = (int)blockIdx.x;
   if (b < nz * A0.nS1) {
     const int z = b / A0.nS1;
-    if (A0.probe & 16) return;
+    if constexpr (probe::atq_no_s1_wgs) return;
     atq_s1_part(at_linear(A0, g, z), b - z * A0.nS1);
     return;
   }
@@ -704,7 +713,7 @@ PT2Q_DEV void atq_block_body(const BlockArgs& A0, const Grp& g, CoeffArgs K, int
     coeff_part(at_linear(A0, g, z), K, b - z * cgrid);
     return;
   }
-  if (A0.probe & 64) return;
+  if constexpr (probe::atq_idle_rows) return;
   const int z = b / rowgrid;
   const BlockArgs A = at_linear(A0, g, z);
   const int wave = threadIdx.x >> 6;
@@ -862,9 +871,10 @@ __global__ void count_zero_rows_kernel(const float* T, long ldt, int n, int b, i
 // waves of the workgroup through L1) or 64 B of one row (row-major).  The codes live in the
 // output array T between passes.  Passes: sum(w); sum|w - mu|; init (writes T, also the first
 // grid's partials); one pass per ITF iteration (round + the next grid's partials); AGA; E.
-// waves per workgroup (4 rows each): pt2q_tuning().wide_waves (4 or 8), up to WIDE_WAVES_MAX
+// waves per workgroup (4 rows each); the kernels' register budget stays the one of launch bounds
+// for up to WIDE_WAVES_MAX waves
+constexpr int WIDE_WAVES = 4;
 constexpr int WIDE_WAVES_MAX = 8;
-inline int wide_waves() { return pt2q_tuning().wide_waves; }
 
 struct WideArgs {
   int mode;          // PT2Q_STAGE_* ; BLOCK = fused init+ITF+AGA+E of the block loop
@@ -1192,31 +1202,30 @@ int pt2q_launch_atq_block(const float* Wt, long ldw, int n, const int* blk, int 
   if (b > 512) {
     WideArgs WA{MODE_BLOCK, Wt, ldw, n, b, blk, S1, d, max_iter, alpha, mu, Tt, ldt, Et, lde,
                 iters, counters, 0};
-    const int wgrid = ceil_div(n, 4 * wide_waves());
-    hipLaunchKernelGGL(atq_wide_block_kernel<LayFM>, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+    const int wgrid = ceil_div(n, 4 * WIDE_WAVES);
+    hipLaunchKernelGGL(atq_wide_block_kernel<LayFM>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
     PT2Q_LAUNCH_CHECK();
-    hipLaunchKernelGGL(atq_wide_zero_fixup_kernel<LayFM>, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+    hipLaunchKernelGGL(atq_wide_zero_fixup_kernel<LayFM>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
     PT2Q_LAUNCH_CHECK();
     if (Hinv && nr > 0) return pt2q_launch_ef_coeffs(Hinv, ldh, blk, b, rem, nr, C, ldc, st);
     return PT2Q_OK;
   }
   const int nS1 = (G && S1 && s1sync && b <= 128) ? ceil_div(b, 8) : 0;
   BlockArgs A{Wt, ldw, n, b, blk, S1, d, max_iter, alpha, mu, Tt, ldt, Et, lde, iters, counters, iters_part,
-              G, ldg, nS1, s1sync, (float*)S1, (float*)d, status, pt2q_tuning().spin_cap_fallback,
-              pt2q_tuning().atq_probe};
+              G, ldg, nS1, s1sync, (float*)S1, (float*)d, status, pt2q_spin_caps().spin_cap_fallback};
   // the EF coefficient workgroups (Hinv given, columns left): COEF_SPAN columns e of one k row each
   const int per_k = (Hinv && nr > 0) ? ceil_div(nr, COEF_SPAN) : 0;
   const CoeffArgs K{Hinv, ldh, rem, nr, b, C, ldc, per_k > 0 ? per_k : 1};
-  const int cgrid = (pt2q_tuning().atq_probe & 2) ? 0 : per_k * b;
+  const int cgrid = probe::atq_no_coeff ? 0 : per_k * b;
   return dispatch_ns(b, [&](auto ns) {
     constexpr int NS = decltype(ns)::value;
     // the six-wave variant only where it costs no spills: full 128-column blocks
     constexpr int OCC = NS == 8 ? 6 : 0;
     // 16-byte staged rows (block_rows_vec): full 128-column blocks, 16-byte aligned pieces
     const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-    const bool vec = NS == 8 && b == 128 && pt2q_tuning().atq_vec && n % 16 == 0 && al16(Wt) && ldw % 4 == 0 &&
+    const bool vec = NS == 8 && b == 128 && n % 16 == 0 && al16(Wt) && ldw % 4 == 0 &&
                      al16(Tt) && ldt % 16 == 0 && (!Et || (al16(Et) && lde % 4 == 0)) && g.ws % 16 == 0;
-    const bool occ = !vec && OCC && b == 16 * NS && pt2q_tuning().atq_occ == 6;
+    const bool occ = !vec && OCC && b == 16 * NS;
     // row workgroups: RG groups of 4 rows per wave (atq_rg; 4 in the staged form)
     const int rg = vec ? 4 : occ ? atq_rg<NS, OCC>() : atq_rg<NS, 0>();
     const int grid = ceil_div(n, ROWS_PER_WG * rg);
@@ -1224,10 +1233,8 @@ int pt2q_launch_atq_block(const float* Wt, long ldw, int n, const int* blk, int 
     if (b == 16 * NS) {
       if (vec)
         hipLaunchKernelGGL((atq_block_kernel<NS, true, 0, NS == 8>), gd, dim3(256), 0, st, A, g, K, grid, cgrid);
-      else if (occ)
+      else  // (occ, or NS > 8 where OCC = 0)
         hipLaunchKernelGGL((atq_block_kernel<NS, true, OCC>), gd, dim3(256), 0, st, A, g, K, grid, cgrid);
-      else
-        hipLaunchKernelGGL((atq_block_kernel<NS, true, 0>), gd, dim3(256), 0, st, A, g, K, grid, cgrid);
     } else {
       hipLaunchKernelGGL((atq_block_kernel<NS, false, 0>), gd, dim3(256), 0, st, A, g, K, grid, cgrid);
     }
@@ -1248,7 +1255,7 @@ int pt2q_launch_atq_wide_rm(const void* W, int wdtype, long ldw, int n, int b, c
                             int* counters, hipStream_t st) {
   WideArgs WA{MODE_BLOCK, (const float*)W, ldw, n, b, nullptr, S1, d, max_iter, alpha, mu, T, ldt, nullptr, 0,
               iters, counters, 0};
-  const int wgrid = ceil_div(n, 4 * wide_waves());
+  const int wgrid = ceil_div(n, 4 * WIDE_WAVES);
   const bool pc = pt2q_atq_pc_supported(W, wdtype, ldw, b);  // codes held on-chip (atq_pc.hip)
   auto go = [&](auto lay) {
     typedef decltype(lay) L;
@@ -1257,10 +1264,10 @@ int pt2q_launch_atq_wide_rm(const void* W, int wdtype, long ldw, int n, int b, c
                                         counters, st);
       if (rc != PT2Q_OK) return rc;
     } else {
-      hipLaunchKernelGGL(atq_wide_block_kernel<L>, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+      hipLaunchKernelGGL(atq_wide_block_kernel<L>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
       PT2Q_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(atq_wide_zero_fixup_kernel<L>, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+    hipLaunchKernelGGL(atq_wide_zero_fixup_kernel<L>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
     PT2Q_LAUNCH_CHECK();
     return PT2Q_OK;
   };
@@ -1293,7 +1300,7 @@ int pt2q_launch_atq_rm_group(int count, const PcLinear* lin, int wdtype, int m, 
     G.a[z] = WideArgs{MODE_BLOCK, (const float*)L.W, L.ldw, L.n, m, nullptr, L.S1, L.d, max_iter, L.alpha, L.mu,
                       L.T, L.ldt, nullptr, 0, L.iters, L.counters, 0};
   }
-  const int wgrid = ceil_div(nmax, 4 * wide_waves());
+  const int wgrid = ceil_div(nmax, 4 * WIDE_WAVES);
   auto go = [&](auto lay) {
     typedef decltype(lay) L;
     if (pc) {
@@ -1301,12 +1308,12 @@ int pt2q_launch_atq_rm_group(int count, const PcLinear* lin, int wdtype, int m, 
       if (rc != PT2Q_OK) return rc;
     } else {
       for (int z = 0; z < count; ++z) {
-        hipLaunchKernelGGL(atq_wide_block_kernel<L>, dim3(ceil_div(lin[z].n, 4 * wide_waves())),
-                           dim3(64 * wide_waves()), 0, st, G.a[z]);
+        hipLaunchKernelGGL(atq_wide_block_kernel<L>, dim3(ceil_div(lin[z].n, 4 * WIDE_WAVES)),
+                           dim3(64 * WIDE_WAVES), 0, st, G.a[z]);
         PT2Q_LAUNCH_CHECK();
       }
     }
-    hipLaunchKernelGGL(atq_wide_zero_fixup_group_kernel<L>, dim3(wgrid, count), dim3(64 * wide_waves()), 0, st, G);
+    hipLaunchKernelGGL(atq_wide_zero_fixup_group_kernel<L>, dim3(wgrid, count), dim3(64 * WIDE_WAVES), 0, st, G);
     PT2Q_LAUNCH_CHECK();
     return PT2Q_OK;
   };
@@ -1344,14 +1351,14 @@ extern "C" int pt2q_atq_stage(int mode, const float* W, int64_t ldw, int n, int 
   if (b > 512) {
     WideArgs WA{mode, Wp, ldw, n, b, nullptr, S1, d_dev, max_iter, alpha, mu, T,
                 ldt, nullptr, 0, iters_dev, zero_rows, 0};
-    const int wgrid = ceil_div(n, 4 * wide_waves());
+    const int wgrid = ceil_div(n, 4 * WIDE_WAVES);
     if (mode == PT2Q_STAGE_FULL) {
       if (hipMemsetAsync(zero_rows, 0, sizeof(int), st) != hipSuccess) return PT2Q_E_HIP;
-      hipLaunchKernelGGL(atq_wide_stage_kernel, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+      hipLaunchKernelGGL(atq_wide_stage_kernel, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
       PT2Q_LAUNCH_CHECK();
       WA.pass = 1;
     }
-    hipLaunchKernelGGL(atq_wide_stage_kernel, dim3(wgrid), dim3(64 * wide_waves()), 0, st, WA);
+    hipLaunchKernelGGL(atq_wide_stage_kernel, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
     PT2Q_LAUNCH_CHECK();
     return PT2Q_OK;
   }

@@ -25,6 +25,7 @@
 
 #include "common.hpp"
 #include "internal.hpp"
+#include "probe.hpp"
 
 namespace {
 
@@ -80,8 +81,6 @@ struct PcArgs {
   long ldt;
   int* iters;        // atomicMax of the wave iteration counts
   int* counters;     // [0] rows whose init codes are all zero
-  int probe;         // development knock-outs (PT2Q_ATQ_PROBE, DEV_PROBES builds; results garbage):
-                     // 1 = no code stores, 2 = AGA with S1 = 1 (no S1 loads), 4 = ITF skipped
 };
 
 // A wave's LDS: ONE ring stage (the streamed kernel), then its code masks.  The stage is
@@ -349,35 +348,14 @@ struct PcAgaOut {
       if (TAIL && j >= jn) continue;
       const uint32_t bit = 1u << (PC_J - 1 - j);
       const float t = (mk.x & bit) ? ((mk.y & bit) ? -1.0f : 1.0f) : 0.0f;
-#ifdef PT2Q_DEV_PROBES
-      if (A.probe & 2) {
-        const float w = x[j], cv = 1.0f;
-        pv = fmaf(t, cv, pv);
-        pws = fmaf(w, cv, pws);
-        pwts = fmaf(w * t, cv, pwts);
-        pt2s = fmaf(t * t, cv, pt2s);
-        if (R.valid && !(A.probe & 1)) trow[16 * j] = (TO)t;
-        continue;
-      }
-      if (A.probe & 1) {
-        if (s1) {
-          const float w = x[j], cv = s1[16 * j];
-          pv = fmaf(t, cv, pv);
-          pws = fmaf(w, cv, pws);
-          pwts = fmaf(w * t, cv, pwts);
-          pt2s = fmaf(t * t, cv, pt2s);
-        }
-        continue;
-      }
-#endif
-      if (s1) {
-        const float w = x[j], cv = s1[16 * j];
+      if (s1 || probe::pc_s1_one) {
+        const float w = x[j], cv = probe::pc_s1_one ? 1.0f : s1[16 * j];
         pv = fmaf(t, cv, pv);
         pws = fmaf(w, cv, pws);
         pwts = fmaf(w * t, cv, pwts);
         pt2s = fmaf(t * t, cv, pt2s);
       }
-      if (R.valid) trow[16 * j] = (TO)t;
+      if (R.valid && !probe::pc_no_codes) trow[16 * j] = (TO)t;
     }
   }
 };
@@ -404,10 +382,7 @@ PT2Q_DEV void pc_rows(R& rows) {
   if (rows.valid && rows.l == 0 && cnt == 0.0f) atomicAdd(&A.counters[0], 1);
   // iterative_ternary_fitting (quantizer.py:136-175), wave-level stop (atq.hip wide_itf)
   int it = 0;
-  bool any = true;
-#ifdef PT2Q_DEV_PROBES
-  if (A.probe & 4) any = false;
-#endif
+  bool any = !probe::pc_no_itf;
   for (; it < A.max_iter; ++it) {
     if (!any) break;
     {
@@ -520,7 +495,6 @@ __global__ __launch_bounds__(64 * PCR_WAVES) __attribute__((amdgpu_waves_per_eu(
 // Whether the streamed per-channel kernel takes this call (else atq.hip's wide kernel): 16-byte
 // aligned rows whose length is whole 16-byte pieces, and the LDS the wave areas need.
 bool pt2q_atq_pc_supported(const void* W, int wdtype, long ldw, int m) {
-  if (!pt2q_tuning().atq_pc) return false;
   const int E = wdtype == PT2Q_F32 ? 4 : 2;
   if (wdtype != PT2Q_F32 && wdtype != PT2Q_F16 && wdtype != PT2Q_BF16) return false;
   if (((uintptr_t)W & 15) != 0 || (ldw * E) % 16 != 0 || (m * E) % 16 != 0 || m <= 512) return false;
@@ -533,15 +507,14 @@ bool pt2q_atq_pc_supported(const void* W, int wdtype, long ldw, int m) {
 int pt2q_launch_atq_pc_group(int count, const PcLinear* lin, int wdtype, int m, int max_iter, int tdtype,
                              hipStream_t st) {
   if (count <= 0 || count > PT2Q_PC_GROUP_MAX) return PT2Q_E_ARG;
-  const bool regs = m == PC_COLS * PCR_NW && wdtype == PT2Q_BF16 && pt2q_tuning().atq_pc_regs;
+  const bool regs = m == PC_COLS * PCR_NW && wdtype == PT2Q_BF16;
   const int rows_wg = 4 * (regs ? PCR_WAVES : PC_WAVES);
   PcGroup G{};
   G.count = count;
   int wg = 0;
   for (int z = 0; z < count; ++z) {
     const PcLinear& L = lin[z];
-    G.a[z] = PcArgs{L.W, L.ldw, L.n, m, L.S1, L.d, max_iter, L.alpha, L.mu, L.T, L.ldt, L.iters, L.counters,
-                    pt2q_tuning().atq_probe};
+    G.a[z] = PcArgs{L.W, L.ldw, L.n, m, L.S1, L.d, max_iter, L.alpha, L.mu, L.T, L.ldt, L.iters, L.counters};
     G.wg0[z] = wg;
     wg += ceil_div(L.n, rows_wg);
   }

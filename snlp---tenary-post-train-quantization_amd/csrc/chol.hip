@@ -388,7 +388,6 @@ int pt2q_launch_cholesky_inverse(const float* H, long ldh, int m, float* Hinv, l
     PT2Q_LAUNCH_CHECK();
   }
   int rc;
-  const Pt2qTuning& tu = pt2q_tuning();
   // panel solve + in-block inverse of the block at p0 (its diagonal factor done: `factored`)
   auto factor = [&](int p0, int nb, bool factored) -> int {
     if (!factored) {
@@ -396,7 +395,7 @@ int pt2q_launch_cholesky_inverse(const float* H, long ldh, int m, float* Hinv, l
       PT2Q_LAUNCH_CHECK();
     }
     const int rest = m - p0 - nb;
-    if (nb == NB && tu.chol_lane) {  // whole blocks: one lane per column / row
+    if (nb == NB) {  // whole blocks: one lane per column / row
       const int npanel = rest > 0 ? (int)ceil_div((long)rest, 256) : 0;
       const int ninv = (int)ceil_div((long)(p0 + nb), 256);
       hipLaunchKernelGGL(chol_panel_trtri_lane_kernel, dim3(npanel + ninv, batch), dim3(256), 0, st, U, ld, p0, m,
@@ -416,12 +415,11 @@ int pt2q_launch_cholesky_inverse(const float* H, long ldh, int m, float* Hinv, l
   // columns of the inverse get the block's terms by rank-64 strip updates, whose first tile is
   // the next diagonal block, factored in the same launch); after the panel, its rank-CP terms
   // (gemmx) as described above.  Every chain takes its terms in ascending k.
-  const int tp = tu.chol_panel;
   // look-ahead from m > 6144 (measured: 4096 3.07 -> 3.24 ms with it, 11008 19.7 -> 18.6 ms with
   // it and 512-row panels); panel rows (a multiple of NB): 512, or 1024 for a large m alone
   // (a batch fills the chip by itself: no look-ahead)
-  const bool ahead = tu.chol_lookahead && m > 6144 && batch == 1;
-  const int CP = tp >= NB ? tp / NB * NB : (m > 6144 && !ahead ? 1024 : 512);
+  const bool ahead = m > 6144 && batch == 1;
+  const int CP = m > 6144 && !ahead ? 1024 : 512;
   CholSide* side = nullptr;
   if (ahead && m > CP + CP && (rc = chol_side(st, side)) != PT2Q_OK) return rc;
   bool factored = false, pending = false;  // pending: side-stream terms not yet joined
@@ -435,8 +433,8 @@ int pt2q_launch_cholesky_inverse(const float* H, long ldh, int m, float* Hinv, l
   // rank-SP chain GEMM once the sub-panel is done -- the same terms in the same ascending order
   // (inverse columns of later sub-panels get the zero terms of rows below their diagonal, exact
   // no-ops), with a quarter of the strip updates' read-modify-write traffic at SP = CP / 4.
-  const int SPt = tu.chol_subpanel >= NB ? tu.chol_subpanel / NB * NB : CP;
-  const int SP = (SPt < CP && CP % SPt == 0) ? SPt : CP;
+  constexpr int SP = 256;
+  static_assert(SP % NB == 0 && 512 % SP == 0, "sub-panels: whole blocks, whole panels");
   for (int P0 = 0; P0 < m; P0 += CP) {
     const int Pend = (m - P0 < CP) ? m : P0 + CP;
     for (int Q0 = P0; Q0 < Pend; Q0 += SP) {

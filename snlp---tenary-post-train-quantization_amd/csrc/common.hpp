@@ -114,66 +114,22 @@ constexpr int SUMN_LDS_MAX = 12288;  // floats staged in LDS by block_sumn_lds u
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
 
-// ---- Launch configuration fixed at library load.
-// The production path has no tunables; these development overrides (PT2Q_* environment
-// variables, used only by the tools/ probes) are read ONCE when libpt2q.so is loaded, never in a
-// launch path.  Defaults are the measured best configuration.
-struct Pt2qTuning {
-  int gram_super = 0;          // PT2Q_GRAM_SUPER: 16-bit Gram super-block side (0: by m)
-  int gram_groups = 8;         // PT2Q_GRAM_GROUPS: XCD groups of the 16-bit Gram split
-  int gram_cus = 0;            // PT2Q_GRAM_CUS: CUs the batched Gram may hold (0: all)
-  bool gram_split = true;      // PT2Q_GRAM_STREAMK=0: one chain per tile, no split
-  bool gram_pair = true;       // PT2Q_GRAM_PAIR=0: no tile-pair teams
-  bool gram_dp = true;         // PT2Q_GRAM_DP=0: no data-parallel waves
-  bool gram_wide = true;       // PT2Q_GRAM_WIDE=0: no 256 x 256 tiles
-  int gram_seglen = 0;         // PT2Q_GRAM_SEGLEN: f32 stream-K segment override
-  int gemm_tile = 0;           // PT2Q_GEMM_TILE: 1 = 128x128, 6 = 64x64
-  bool rank_update = true;     // PT2Q_RANK_UPDATE=0: generic grouped GEMM for Cholesky updates
-  bool chol_lookahead = true;  // PT2Q_CHOL_LOOKAHEAD=0: the trailing updates on the main stream only
-  int chol_panel = 0;          // PT2Q_CHOL_PANEL: rows per rank-P Cholesky update (0: by m)
-  int chol_subpanel = 256;     // PT2Q_CHOL_SUBPANEL: rank-64 strip updates only inside sub-panels of
-                               // this many rows, rank-SP updates (gemmx) to the rest of the panel (0: off)
-  bool wbar_fused = true;      // PT2Q_WBAR_FUSED=0: three SSR-mean launches
-  bool ef_wbar = true;         // PT2Q_EF_WBAR=0: the SSR mean pass reads W again (no EF partials)
-  bool sim_split = true;       // PT2Q_SIM_SPLIT=0: one wave per column for n > 4096 (256 VGPRs)
-  int gemmx_stages = 2;        // PT2Q_GEMMX_STAGES: LDS stages of the f32 chain GEMM (2: 64 KiB, 2 WGs per CU;
-                               // batched inverse 596 -> 534 ms per 7B step vs 3)
-  bool chol_lane = true;       // PT2Q_CHOL_LANE=0: the four-lanes-per-column panel / in-block inverse
-  bool gemmx_gram = true;      // PT2Q_GEMMX_GRAM=0: batched f32 Grams on the generic GEMM
-  bool s1_in_atq = true;       // PT2Q_S1_IN_ATQ=0: S1/d in the top-k launch
-  bool ef_kernel = true;       // PT2Q_EF_GEMM=0: error feedback through the generic GEMM
-  int ef_v2 = 1;               // PT2Q_EF_V2: 1 = ef2_gemm_kernel (two workgroups per CU, default), 0 = ef_gemm_kernel
-  bool ef2_g1lds = true;       // PT2Q_EF2_G1LDS=0: column group 1's old values loaded in the epilogue
-  int ef2_per_cu = 2;          // PT2Q_EF2_PER_CU: ef2 workgroups per CU (1 or 2)
-  int ef2_teams = 1;           // PT2Q_EF2_TEAMS: 2 = one 8-wave workgroup of two barrier-coupled teams per CU
-  int ef2_team_offset = 5;     // PT2Q_EF2_TEAM_OFFSET: barriers team 1 starts behind team 0
-  int ef2_stagger = 0;         // PT2Q_EF2_STAGGER: ef2 start de-phasing (0: off)
-  int ef2_probe = 0;           // PT2Q_EF2_PROBE: ef2 knock-out mask (tools only; results garbage)
-  int atq_probe = 0;           // PT2Q_ATQ_PROBE (DEV_PROBES builds only; results garbage): block-ATQ
-                               // knock-outs, 1 = rows skip the S1 wait, 2 = no coefficient workgroups,
-                               // 4 = rows skip ITF, 8 / 128 / 256 = no code / error-term / scale
-                               // stores, 16 = no S1 workgroups, 32 = no row gathers, 64 = idle rows
-  bool gram_order = true;      // PT2Q_GRAM_ORDER=0: batched Gram in the super-block tile order
-  bool atq_vec = true;         // PT2Q_ATQ_VEC=0: 128-column block ATQ with per-element row stores
-  int wide_waves = 4;          // PT2Q_WIDE_WAVES: waves (4 rows each) per wide-ATQ workgroup (4 or 8)
-  int atq_occ = 6;             // PT2Q_ATQ_OCC: block-ATQ waves per SIMD floor (6, or 0: compiler's)
-  bool atq_pc = true;          // PT2Q_ATQ_PC=0: per-channel rows on the old streaming wide kernel
-  bool atq_pc_regs = true;     // PT2Q_ATQ_PC_REGS=0: m = 5120 rows streamed like the others
+// ---- Spin caps, fixed at library load (the launch configuration itself has no tunables).
+struct Pt2qSpinCaps {
   // Cross-workgroup waits poll at most this many times (each poll sleeps ~64-128 cycles), i.e.
   // seconds, before they give up and report PT2Q_E_STALL.  PT2Q_DEBUG_SPIN_CAP overrides both
   // (0: every hand-off reports a stall -- tests force the reporting path with it).
   long spin_cap_long = 1l << 28;   // Gram partial-tile hand-offs (a long chain may be in flight)
-  long spin_cap_short = 1l << 26;  // in-launch hand-offs (S1 / d, top-k picks)
   long spin_cap_fallback = 1l << 13;  // ATQ S1 / d wait: polls before the wave forms S1 / d itself
 };
-const Pt2qTuning& pt2q_tuning();  // api.hip
+const Pt2qSpinCaps& pt2q_spin_caps();  // api.hip
 
 // ---- Stall reporting.
 // Every call that takes a workspace reserves its first PT2Q_STATUS_BYTES (pt2q.h) for a status
 // word (int, zeroed by the call).  A wait on another workgroup that gives up ORs its bit into that
 // word instead of carrying on silently; the host reads it after the stream completes and raises
 // PT2Q_E_STALL (_lib.check_status).
-enum : int { STALL_GRAM = 0x1, STALL_ATQ_S1 = 0x2, STALL_TOPK = 0x4 };
+enum : int { STALL_GRAM = 0x1, STALL_ATQ_S1 = 0x2 };
 
 // Poll *flag until it is >= v.  Returns false (and marks *status) if the wait gave up after `cap`
 // polls.  Call from one thread; the caller orders the data it then reads (fence / sc1 loads).

@@ -546,9 +546,6 @@ int launch_dt(const GemmDesc& g, hipStream_t st) {
   };
   const double slots = 256.0;
   long c128 = count(128), c64 = count(64);
-  const int force = pt2q_tuning().gemm_tile;
-  if (force == 1) return launch_t<128, 128, TIn>(g, st);
-  if (force == 6) return launch_t<64, 64, TIn>(g, st);
   // efficiency = useful tiles / (rounds * slots); 64x64 tiles cost 1/4 of a 128x128 tile
   double r128 = std::ceil(c128 / slots), r64 = std::ceil(c64 / slots);
   double t128 = r128 * 4.0, t64 = r64 * 1.0 * 1.15;  // 64x64: ~15% lower per-tile efficiency
@@ -558,7 +555,6 @@ int launch_dt(const GemmDesc& g, hipStream_t st) {
 
 template <typename TIn>
 int launch_streamk(const GemmDesc& g, int* flags, int nflags, hipStream_t st, int* status) {
-  const Pt2qTuning& tu = pt2q_tuning();
   const int T = ceil_div(g.M, 128);
   const int ntile = T * (T + 1) / 2;
   if (ntile > nflags) return PT2Q_E_WORKSPACE;
@@ -584,15 +580,11 @@ int launch_streamk(const GemmDesc& g, int* flags, int nflags, hipStream_t st, in
     }
   }
   // flags: ntile tile flags, status, unit counter
-  if (tu.gram_seglen >= 64) {
-    seglen = tu.gram_seglen / (2 * BK) * (2 * BK);
-    nseg = ceil_div(g.K, seglen);
-  }
   if (hipMemsetAsync(flags, 0, sizeof(int) * (ntile + 2), st) != hipSuccess) return PT2Q_E_HIP;
   if (!status) status = flags + ntile;
   int* counter = flags + ntile + 1;
   hipLaunchKernelGGL(kern, dim3(P), dim3(256), 0, st, g, T, nseg, seglen, flags, counter, status,
-                     tu.spin_cap_long);
+                     pt2q_spin_caps().spin_cap_long);
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;
 }
@@ -831,7 +823,7 @@ int pt2q_launch_gemm2(const GemmDesc& g0, const GemmDesc& g1, hipStream_t st, fl
   if (g0.in_dtype != PT2Q_F32 || g1.in_dtype != PT2Q_F32) return PT2Q_E_ARG;
   const int nb = g0.batch > 1 ? g0.batch : 1;
   if (nb != (g1.batch > 1 ? g1.batch : 1) || (nb > 1 && g0.bstride != g1.bstride)) return PT2Q_E_ARG;
-  if (ru_ok(g0) && ru_ok(g1) && pt2q_tuning().rank_update) {
+  if (ru_ok(g0) && ru_ok(g1)) {
     int tm0, tn0, tm1, tn1;
     const long n0 = tiles_of<RU_T, RU_T>(g0, tm0, tn0), n1 = tiles_of<RU_T, RU_T>(g1, tm1, tn1);
     if (n0 + n1 <= 0) return PT2Q_OK;
@@ -888,10 +880,8 @@ int pt2q_launch_gram_f32_batched(const float* const* X, long N, int m, long ldx,
                                  hipStream_t st) {
   if (batch <= 0 || batch > GF_MAX || m <= 0 || N < 0 || N > INT_MAX || ldx < m || !G) return PT2Q_E_ARG;
   // the LDS-DMA kernel where the operands allow it (aligned rows)
-  if (pt2q_tuning().gemmx_gram) {
-    const int rc = pt2q_launch_gemmx_gram(X, N, m, ldx, G, gstride, batch, st);
-    if (rc != PT2Q_E_UNSUPPORTED) return rc;
-  }
+  const int rc = pt2q_launch_gemmx_gram(X, N, m, ldx, G, gstride, batch, st);
+  if (rc != PT2Q_E_UNSUPPORTED) return rc;
   GemmDesc g{};
   g.M = m; g.N = m; g.K = (int)N;
   g.lda = ldx; g.a_layout = LAY_KMAJOR;
@@ -934,8 +924,7 @@ int pt2q_launch_gram(const GemmDesc& g, int* flags, hipStream_t st, int* status)
   if (g.in_dtype == PT2Q_F16 || g.in_dtype == PT2Q_BF16) return pt2q_launch_gram16(g, flags, st, status);
   const int T = ceil_div(g.M, 128);
   const long ntile = (long)T * (T + 1) / 2;
-  const bool allow = pt2q_tuning().gram_split;
-  if (flags && allow && (g.mode == GEMM_STORE || g.mode == GEMM_CHAIN_POS) && g.upper && g.mirror && g.M == g.N &&
+  if (flags && (g.mode == GEMM_STORE || g.mode == GEMM_CHAIN_POS) && g.upper && g.mirror && g.M == g.N &&
       ntile >= 128 && g.K >= 16384) {
     if (g.in_dtype == PT2Q_F32) return launch_streamk<float>(g, flags, (int)ntile, st, status);
   }

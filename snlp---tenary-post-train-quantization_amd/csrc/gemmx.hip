@@ -27,13 +27,12 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int XT = 128;              // tile side
 constexpr int XROW = XT * 4;         // 512 B per k row of a panel
 
-// ring geometry: KR k rows per stage, NS stages (LDS = NS * 2 * KR * 512 B)
-template <int KR>
-struct XGeo {
-  static constexpr int PANEL = KR * XROW;       // one operand's rows of a stage
-  static constexpr int STG = 2 * PANEL;         // A + B panels
-  static constexpr int DMA = PANEL / 1024 / 4;  // DMA wave-instructions per wave per panel
-};
+// ring geometry: XNS stages of XK k rows (64 KiB of LDS: two workgroups per CU; three stages of
+// 32 rows or four / five of 16 measured slower)
+constexpr int XNS = 2, XK = 32;
+constexpr int XPANEL = XK * XROW;        // one operand's rows of a stage
+constexpr int XSTG = 2 * XPANEL;         // A + B panels
+constexpr int XDMA = XPANEL / 1024 / 4;  // DMA wave-instructions per wave per panel
 
 __device__ uint4 gxz_zero16[4];      // the source of out-of-range chunks (zero-initialised)
 
@@ -73,13 +72,11 @@ PT2Q_DEV int x_xcd_remap(int b, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + b / 8;
 }
 
-// One panel of one stage: rows [k0, k0 + KR) (valid below kend) x columns [d0, d0 + 128) (valid
+// One panel of one stage: rows [k0, k0 + XK) (valid below kend) x columns [d0, d0 + 128) (valid
 // below DMAX) of a K-major operand, into panel memory `pan` (swizzled).  Lane l of the wave's
 // q-th instruction fills LDS chunk L = (wave * DMA + q) * 64 + l: row L / 32, position L % 32,
 // which holds global chunk (L % 32) ^ ((row & 1) << 3).
-template <int KR>
 PT2Q_DEV void x_panel_dma(const float* base, long ld, int d0, int DMAX, int k0, int kend, uint8_t* pan) {
-  constexpr int XDMA = XGeo<KR>::DMA;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   typedef __attribute__((address_space(3))) void* lptr;
@@ -95,12 +92,10 @@ PT2Q_DEV void x_panel_dma(const float* base, long ld, int d0, int DMAX, int k0, 
   }
 }
 
-// Fast staging of a whole in-range panel (rows [k0, k0 + KR) below kend, columns [d0, d0 + 128)
+// Fast staging of a whole in-range panel (rows [k0, k0 + XK) below kend, columns [d0, d0 + 128)
 // below DMAX): this lane's byte offsets from the panel's first element, fixed for the launch, and a
 // scalar base -- s_mov m0 + one global_load_lds per chunk instead of per-lane address math.
-template <int KR>
-PT2Q_DEV void x_panel_voff(long ld, uint32_t (&vo)[XGeo<KR>::DMA]) {
-  constexpr int XDMA = XGeo<KR>::DMA;
+PT2Q_DEV void x_panel_voff(long ld, uint32_t (&vo)[XDMA]) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
 #pragma unroll
@@ -111,10 +106,8 @@ PT2Q_DEV void x_panel_voff(long ld, uint32_t (&vo)[XGeo<KR>::DMA]) {
   }
 }
 
-template <int KR>
-PT2Q_DEV void x_panel_dma_fast(const float* base, long ld, int d0, int k0, const uint32_t (&vo)[XGeo<KR>::DMA],
+PT2Q_DEV void x_panel_dma_fast(const float* base, long ld, int d0, int k0, const uint32_t (&vo)[XDMA],
                                uint32_t pan) {
-  constexpr int XDMA = XGeo<KR>::DMA;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const char* sb = (const char*)(base + (long)k0 * ld + d0);
 #pragma unroll
@@ -148,17 +141,16 @@ PT2Q_DEV void x_read(XOps& o, uint32_t aA0, uint32_t aA1, uint32_t aB0, uint32_t
 
 // the next stage's fast DMAs, one A and one B chunk after the first MFMA of k-pair q (q < DMA), so
 // their issue sits in MFMA shadows instead of in front of the stage (on = false: nothing)
-template <int KR>
 struct XStageIO {
   const char* sbA;
   const char* sbB;
-  const uint32_t (&voA)[XGeo<KR>::DMA];
-  const uint32_t (&voB)[XGeo<KR>::DMA];
+  const uint32_t (&voA)[XDMA];
+  const uint32_t (&voB)[XDMA];
   uint32_t mA, mB;
   bool on;
   template <int S>
   PT2Q_DEV void at() {
-    if constexpr (S < XGeo<KR>::DMA) {
+    if constexpr (S < XDMA) {
       if (on) {
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voA[S]), "s"(sbA),
                      "s"(mA + S * 1024)
@@ -206,18 +198,6 @@ PT2Q_DEV void x_chain(f32x16 (&acc)[2][2], XOps& o, uint32_t aA0, uint32_t aA1, 
   }
 }
 
-// wait until the y youngest stages (D DMAs each, 0 <= y <= 4) may stay in flight
-template <int D>
-PT2Q_DEV void x_vmwait(int y) {
-  switch (y) {
-    case 0: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    case 1: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(D) : "memory"); break;
-    case 2: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * D) : "memory"); break;
-    case 3: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(3 * D) : "memory"); break;
-    default: asm volatile("s_waitcnt vmcnt(%0)" ::"n"(4 * D) : "memory"); break;
-  }
-}
-
 struct XArgs {
   GemmDesc g;
   int tiles_m, tiles_n;
@@ -225,10 +205,7 @@ struct XArgs {
 };
 
 // One workgroup's tile of item blockIdx.y: operands Ab / Bb, output Cz (the item's bases).
-template <int NS, int KR>
 PT2Q_DEV void gemmx_tile(const XArgs& X, const float* Ab, const float* Bb, float* const Cz, uint8_t* smem) {
-  using GE = XGeo<KR>;
-  constexpr int XSTG = GE::STG, XPANEL = GE::PANEL, XDMA = GE::DMA, XK = KR;
   const GemmDesc& g = X.g;
   int ti, tj;
   const int bid = blockIdx.x;
@@ -268,25 +245,23 @@ PT2Q_DEV void gemmx_tile(const XArgs& X, const float* Ab, const float* Bb, float
       }
     }
   asm volatile("" ::: "memory");
-  // prologue DMA: stages 0 .. NS-2 (stage p is whole -- the fast path -- when p < nfull)
+  // prologue DMA: stage 0 (stage p is whole -- the fast path -- when p < nfull)
   uint32_t voA[XDMA], voB[XDMA];
-  x_panel_voff<KR>(g.lda, voA);
-  x_panel_voff<KR>(g.ldb, voB);
+  x_panel_voff(g.lda, voA);
+  x_panel_voff(g.ldb, voB);
   const uint32_t ldsb = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;
   const int nfull = (i0 + XT <= g.M && j0 + XT <= g.N) ? (kend - kbeg) / XK : 0;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   auto stage = [&](int p) {
     if (p < nfull) {
-      x_panel_dma_fast<KR>(Ab, g.lda, i0, kbeg + p * XK, voA, ldsb + (uint32_t)((p % NS) * XSTG));
-      x_panel_dma_fast<KR>(Bb, g.ldb, j0, kbeg + p * XK, voB, ldsb + (uint32_t)((p % NS) * XSTG + XPANEL));
+      x_panel_dma_fast(Ab, g.lda, i0, kbeg + p * XK, voA, ldsb + (uint32_t)((p % XNS) * XSTG));
+      x_panel_dma_fast(Bb, g.ldb, j0, kbeg + p * XK, voB, ldsb + (uint32_t)((p % XNS) * XSTG + XPANEL));
     } else {
-      x_panel_dma<KR>(Ab, g.lda, i0, g.M, kbeg + p * XK, kend, smem + (p % NS) * XSTG);
-      x_panel_dma<KR>(Bb, g.ldb, j0, g.N, kbeg + p * XK, kend, smem + (p % NS) * XSTG + XPANEL);
+      x_panel_dma(Ab, g.lda, i0, g.M, kbeg + p * XK, kend, smem + (p % XNS) * XSTG);
+      x_panel_dma(Bb, g.ldb, j0, g.N, kbeg + p * XK, kend, smem + (p % XNS) * XSTG + XPANEL);
     }
   };
-#pragma unroll
-  for (int p = 0; p < NS - 1; ++p)
-    if (p < nst) stage(p);
+  if (nst > 0) stage(0);
   f32x16 acc[2][2];
 #pragma unroll
   for (int rm = 0; rm < 2; ++rm)
@@ -311,21 +286,19 @@ PT2Q_DEV void gemmx_tile(const XArgs& X, const float* Ab, const float* Bb, float
   const uint32_t oB0 = opaddr(XPANEL, wc * 64 + li), oB1 = opaddr(XPANEL, wc * 64 + 32 + li);
   XOps o;
   for (int t = 0; t < nst; ++t) {
-    // stage t landed (this wave's DMAs; stage t+1 may stay in flight), then a raw barrier (the
-    // fence of __syncthreads would wait vmcnt(0)); the barrier also retires every wave's reads
-    // of the slot the next DMA reuses
-    // (younger stages in flight: t+1 .. min(t+NS-2, nst-1))
-    x_vmwait<2 * XDMA>(min(NS - 2, nst - 1 - t));
+    // stage t landed (this wave's DMAs: nothing younger is in flight), then a raw barrier; it
+    // also retires every wave's reads of the slot the next DMA reuses
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");
-    const int tn = t + NS - 1;
+    const int tn = t + 1;
     // a whole next stage goes out inside the chain (XStageIO), any other one here
     const bool fastn = tn < nfull;
     if (tn < nst && !fastn) stage(tn);
-    XStageIO<KR> sio{(const char*)(Ab + (long)(kbeg + tn * XK) * g.lda + i0),
+    XStageIO sio{(const char*)(Ab + (long)(kbeg + tn * XK) * g.lda + i0),
                      (const char*)(Bb + (long)(kbeg + tn * XK) * g.ldb + j0), voA, voB,
-                     ldsb + (uint32_t)((tn % NS) * XSTG + wv * XDMA * 1024),
-                     ldsb + (uint32_t)((tn % NS) * XSTG + XPANEL + wv * XDMA * 1024), tn < nst && fastn};
-    const uint32_t sb = lds0 + (uint32_t)((t % NS) * XSTG);
+                     ldsb + (uint32_t)((tn % XNS) * XSTG + wv * XDMA * 1024),
+                     ldsb + (uint32_t)((tn % XNS) * XSTG + XPANEL + wv * XDMA * 1024), tn < nst && fastn};
+    const uint32_t sb = lds0 + (uint32_t)((t % XNS) * XSTG);
     x_chain<0, XK / 2>(acc, o, sb + oA0, sb + oA1, sb + oB0, sb + oB1, sio);
   }
   // epilogue
@@ -352,11 +325,10 @@ PT2Q_DEV void gemmx_tile(const XArgs& X, const float* Ab, const float* Bb, float
     }
 }
 
-template <int NS, int KR>
 __global__ __launch_bounds__(256) void gemmx_kernel(XArgs X) {
-  __shared__ __attribute__((aligned(1024))) uint8_t smem[NS * XGeo<KR>::STG];
+  __shared__ __attribute__((aligned(1024))) uint8_t smem[XNS * XSTG];
   const long zo = (long)blockIdx.y * X.g.bstride;  // batch item (grid.y)
-  gemmx_tile<NS, KR>(X, (const float*)X.g.A + zo, (const float*)X.g.B + zo, X.g.C + zo, smem);
+  gemmx_tile(X, (const float*)X.g.A + zo, (const float*)X.g.B + zo, X.g.C + zo, smem);
 }
 
 // Symmetric Grams G[z] = X[z]ᵀX[z] of a batch with their own activation pointers: X[z] (N x m,
@@ -365,11 +337,10 @@ struct XPtrs {
   const float* X[PT2Q_GX_PTRS];
 };
 
-template <int NS, int KR>
 __global__ __launch_bounds__(256) void gemmx_gram_kernel(XArgs X, XPtrs P) {
-  __shared__ __attribute__((aligned(1024))) uint8_t smem[NS * XGeo<KR>::STG];
+  __shared__ __attribute__((aligned(1024))) uint8_t smem[XNS * XSTG];
   const float* Xz = P.X[blockIdx.y];
-  gemmx_tile<NS, KR>(X, Xz, Xz, X.g.C + (long)blockIdx.y * X.g.bstride, smem);
+  gemmx_tile(X, Xz, Xz, X.g.C + (long)blockIdx.y * X.g.bstride, smem);
 }
 
 }  // namespace
@@ -398,7 +369,7 @@ int pt2q_launch_gemmx_gram(const float* const* X, long N, int m, long ldx, float
   g.batch = batch; g.bstride = gstride;
   XArgs A{g, ceil_div(m, XT), ceil_div(m, XT), 1};
   const dim3 grid((unsigned)((long)A.tiles_n * (A.tiles_n + 1) / 2), (unsigned)batch);
-  hipLaunchKernelGGL((gemmx_gram_kernel<2, 32>), grid, dim3(256), 0, st, A, P);
+  hipLaunchKernelGGL(gemmx_gram_kernel, grid, dim3(256), 0, st, A, P);
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;
 }
@@ -423,12 +394,7 @@ int pt2q_launch_gemmx(const GemmDesc& g, hipStream_t st) {
     tiles = (long)X.tiles_m * X.tiles_n;
   }
   const dim3 grid((unsigned)tiles, (unsigned)(g.batch > 1 ? g.batch : 1));
-  switch (pt2q_tuning().gemmx_stages) {
-    case 3: hipLaunchKernelGGL((gemmx_kernel<3, 32>), grid, dim3(256), 0, st, X); break;  // 96 KiB
-    case 4: hipLaunchKernelGGL((gemmx_kernel<4, 16>), grid, dim3(256), 0, st, X); break;  // 64 KiB, 2 WGs/CU
-    case 5: hipLaunchKernelGGL((gemmx_kernel<5, 16>), grid, dim3(256), 0, st, X); break;  // 80 KiB, 2 WGs/CU
-    default: hipLaunchKernelGGL((gemmx_kernel<2, 32>), grid, dim3(256), 0, st, X); break;  // 64 KiB, 2 WGs/CU
-  }
+  hipLaunchKernelGGL(gemmx_kernel, grid, dim3(256), 0, st, X);
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;
 }

@@ -36,6 +36,7 @@ constexpr int GX_BSTG = GX_BK * GX_BROW;    // 32 KiB
 constexpr int GX_STG = GX_ASTG + GX_BSTG;   // 48 KiB per stage
 constexpr int GX_LDS = GX_NS * GX_STG;      // 144 KiB
 constexpr int GX_DMA_PER_STAGE = 12;        // LDS-DMA wave-instructions per wave per stage
+constexpr int GX_GROUPS = 8;                // XCD groups of the split (one per XCD)
 
 __device__ uint4 gx_zero16;  // the source of out-of-range chunks (zero-initialised)
 
@@ -958,10 +959,9 @@ int pt2q_launch_gram16_batched(const void* const* X, int dtype, long N, int m, l
     if ((uintptr_t)X[z] % 16) return PT2Q_E_UNSUPPORTED;
     b.X[z] = (const uint16_t*)X[z];
   }
-  const Pt2qTuning& tu = pt2q_tuning();
   b.G = G; b.gstride = gstride; b.ldx = ldx; b.ldc = m;
   b.T = m / GW_B;
-  b.SJ = tu.gram_super > 0 ? tu.gram_super : 8;
+  b.SJ = 8;
   b.K = (int)N;
   b.M = m;
   b.batch = batch;
@@ -969,10 +969,8 @@ int pt2q_launch_gram16_batched(const void* const* X, int dtype, long N, int m, l
   b.total = b.ntile * batch;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  b.NG = std::max(1, tu.gram_groups);
-  // PT2Q_GRAM_CUS (development knob): CUs the batched Gram may hold (one workgroup each)
-  const int use = tu.gram_cus > 0 ? std::min(tu.gram_cus, cus) : cus;
-  b.R = std::max(1, use / b.NG);
+  b.NG = GX_GROUPS;
+  b.R = std::max(1, cus / b.NG);  // one workgroup per CU
   const long grid = std::min<long>(b.total, (long)b.NG * b.R);
   if (grid < (long)b.NG * b.R) {  // fewer tiles than workgroups: one tile each, no team order
     b.NG = 1;
@@ -980,7 +978,7 @@ int pt2q_launch_gram16_batched(const void* const* X, int dtype, long N, int m, l
   }
   b.ord = -1;
   b.upper = upper ? 1 : 0;
-  if (tu.gram_order && b.R == 32 && b.NG * b.R == cus && b.ntile >= 32)
+  if (b.R == 32 && b.NG * b.R == cus && b.ntile >= 32)
     for (int q = 0; q < GO_COUNT; ++q)
       if (go_T[q] == b.T) {
         b.ord = go_off[q];
@@ -1001,23 +999,22 @@ size_t pt2q_gram16_flags_ints(int m) { return (size_t)gx_ntile(m) + 2; }
 int pt2q_launch_gram16(const GemmDesc& g, int* flags, hipStream_t st, int* status) {
   if (g.in_dtype != PT2Q_F16 && g.in_dtype != PT2Q_BF16) return PT2Q_E_ARG;
   if (g.M != g.N || g.A != g.B || g.lda != g.ldb) return PT2Q_E_ARG;
-  const Pt2qTuning& tu = pt2q_tuning();
   const int m = g.M;
   const int TI = ceil_div(m, GX_BM), TJ = ceil_div(m, GX_BN);
   // super-block side ~ the square one XCD's share of the triangle covers
-  const int SJ = tu.gram_super > 0 ? tu.gram_super : (m <= 6144 ? 4 : 8);
+  const int SJ = m <= 6144 ? 4 : 8;
   const long ntile = gx_ntile(m);
   const int Kp = std::max(1, ceil_div(g.K, GX_BK)) * GX_BK;  // K = 0: one all-zero stage
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
   // split when there are more tiles than CUs: NG XCD groups of R workgroups (one per CU)
-  int NG = std::max(1, tu.gram_groups);
+  int NG = GX_GROUPS;
   int R = cus / NG;
-  const bool split = flags && g.mode != GEMM_ADD && tu.gram_split && R > 0 && ntile >= (long)NG * R;
+  const bool split = flags && g.mode != GEMM_ADD && R > 0 && ntile >= (long)NG * R;
   // tile pairs need every column run of the tile order to be even (TI even) and teams of two
-  int P = (split && TI % 2 == 0 && R % 2 == 0 && tu.gram_pair) ? 2 : 1;
+  int P = (split && TI % 2 == 0 && R % 2 == 0) ? 2 : 1;
   // whole data-parallel waves while at least one tile per workgroup is left for stream-K
-  const int D = (split && tu.gram_dp) ? (int)std::max(0l, ntile / (NG * R) - 1) : 0;
+  const int D = split ? (int)std::max(0l, ntile / (NG * R) - 1) : 0;
   unsigned grid;
   if (split) {
     grid = (unsigned)(NG * R);
@@ -1037,12 +1034,12 @@ int pt2q_launch_gram16(const GemmDesc& g, int* flags, hipStream_t st, int* statu
   // data-parallel part keeps every CU busy); mirror stores are float4
   const int TW = m / GW_B;
   const long ntw = (long)TW * (TW + 1) / 2;
-  if (split && dma && tu.gram_wide && m % GW_B == 0 && ntw >= 2l * NG * R && (uintptr_t)g.C % 16 == 0 &&
+  if (split && dma && m % GW_B == 0 && ntw >= 2l * NG * R && (uintptr_t)g.C % 16 == 0 &&
       g.ldc % 4 == 0) {
-    const int SW = tu.gram_super > 0 ? tu.gram_super : 8;
-    const int Dw = tu.gram_dp ? (int)std::max(0l, ntw / (NG * R) - 1) : 0;
+    const int SW = 8;
+    const int Dw = (int)std::max(0l, ntw / (NG * R) - 1);
     hipLaunchKernelGGL(bf ? gram16w_kernel<true> : gram16w_kernel<false>, dim3(grid), dim3(256), 0, st, g, TW, SW,
-                       Kp, ntw, NG, R, Dw, flags, status, tu.spin_cap_long);
+                       Kp, ntw, NG, R, Dw, flags, status, pt2q_spin_caps().spin_cap_long);
     PT2Q_LAUNCH_CHECK();
     return PT2Q_OK;
   }
@@ -1050,7 +1047,7 @@ int pt2q_launch_gram16(const GemmDesc& g, int* flags, hipStream_t st, int* statu
       bf ? (dma ? gram16x_kernel<true, true> : gram16x_kernel<true, false>)
          : (dma ? gram16x_kernel<false, true> : gram16x_kernel<false, false>);
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, g, TI, TJ, SJ, Kp, ntile, NG, R, P, D, flags, status,
-                     tu.spin_cap_long);
+                     pt2q_spin_caps().spin_cap_long);
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;
 }

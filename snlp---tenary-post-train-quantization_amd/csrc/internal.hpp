@@ -78,9 +78,7 @@ int pt2q_launch_ssr_similarity(const float* Wt, long ldw, int n, const int* rem,
                                const Grp* grp = nullptr, bool pre = false);
 inline int pt2q_ssr_counter_ints(int n) { return (n + 255) / 256 + 1; }
 int pt2q_launch_ssr_topk(const float* sim, const int* rem, int r, int b, int* blk, int* newrem,
-                         int64_t* perm_out, hipStream_t st, const float* G = nullptr, long ldg = 0,
-                         float* S1 = nullptr, float* d = nullptr, int* sync = nullptr,
-                         int* status = nullptr, const Grp* grp = nullptr);
+                         int64_t* perm_out, hipStream_t st, const Grp* grp = nullptr);
 int pt2q_launch_select_seq(int mode, int p0, int bs, int m, const int* rem, int* blk,
                            int* newrem, int64_t* perm_out, hipStream_t st, const Grp* grp = nullptr);
 int pt2q_launch_s1_batched(const float* G, long ldg, int m, int batch, long sG, float* S1d, hipStream_t st,

@@ -563,86 +563,23 @@ constexpr int TOPK_HPAD = 257;  // per-wave histogram stride (bank-spread)
 // four 8-bit histogram passes over the orderable value bits find the b-th largest value v*;
 // every value > v* is taken, plus the first (by position) b - #(> v*) values equal to v*; the
 // b picks are then ranked among themselves.  Writes blk (selection order), newrem (ascending,
-// reorder.py:139-141), perm_out (int64, nullable).  With G != nullptr (variant M, b <= 128)
-// the same workgroup then forms S1/d for AGA from the raw Gram over the block it just selected.
-// LDS: region0 (max(r + 32*257, b*(b+1)) words: values + two banks of wave histograms, later the S1 gather),
-// r flag bytes, scan ints, b picks / their values / block indices / partial sums.
-constexpr int S1_ROWS = TOPK_THREADS / 128;  // S1 rows per helper workgroup
-
-// Helper workgroups 1.. of the top-k launch (variant M): wait for workgroup 0's pick, gather
-// rows of G[blk][blk] in parallel and sum each in l order; the last one to finish forms d in j
-// order (the s1_block order).  Workgroup 0 is dispatched first and waits on nobody, so the
-// spin cannot deadlock.  sync[0]: pick published; sync[1]: helpers done.
-
-PT2Q_DEV void s1_helper(const float* G, long ldg, const int* blk, int b, float* S1, float* d,
-                        int* sync, float* gb, int* status, long cap) {
-  const int tid = threadIdx.x, nh = gridDim.x - 1;
-  // hand-offs (pick -> helpers, S1 -> the last helper): write-through (sc1) stores drained
-  // before the flag / counter, sc1 loads on the consuming side, no fences
-  if (tid == 0) wait_flag_ge<1>(&sync[0], 1, cap, status, STALL_TOPK);
-  __syncthreads();
-  PT2Q_TOPK_STAMP(8);
-  const int jj = tid >> 7, l = tid & 127;
-  const int j = (blockIdx.x - 1) * S1_ROWS + jj;
-  if (j < b && l < b) {
-    const int bj = __hip_atomic_load(&blk[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int bl = __hip_atomic_load(&blk[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    gb[jj * 129 + l] = G[(long)bj * ldg + bl];
-  }
-  __syncthreads();
-  if (l == 0 && j < b) {
-    const float* row = gb + jj * 129;
-    float s = 0.0f;
-    int q = 0;
-    for (; q + 8 <= b; q += 8) {
-      float t[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) t[u] = row[q + u];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) s = s + t[u];
-    }
-    for (; q < b; ++q) s = s + row[q];
-    __hip_atomic_store(&S1[j], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __shared__ int last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  PT2Q_TOPK_STAMP(9);
-  if (tid == 0) last = atomicAdd(&sync[1], 1) == nh - 1;
-  __syncthreads();
-  if (!last) return;
-  if (tid < b) gb[tid] = __hip_atomic_load(&S1[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  if (tid == 0) {
-    float dd = 0.0f;
-    for (int q = 0; q < b; ++q) dd = dd + gb[q];
-    *d = dd;
-  }
-}
-
+// reorder.py:139-141), perm_out (int64, nullable).
+// LDS: region0 (r + 32*257 words: values + two banks of wave histograms), r flag bytes, scan ints,
+// b picks / their values (and 2 b spare words the launch keeps in its LDS size).
 __global__ __launch_bounds__(TOPK_THREADS) void ssr_topk_kernel(const float* sim, const int* rem, int r,
                                                                 int b, int* blk, int* newrem,
-                                                                int64_t* perm_out, const float* G,
-                                                                long ldg, float* S1, float* d,
-                                                                int region0, int* sync, int* status,
-                                                                long cap, long zs) {
+                                                                int64_t* perm_out, int region0, long zs) {
   extern __shared__ uint32_t vals[];
-  sim = zws(sim, zs);  // grouped launch (no S1 helpers): linear blockIdx.z's slice
+  sim = zws(sim, zs);  // grouped launch: linear blockIdx.z's slice
   rem = zws(rem, zs);
   blk = zws(blk, zs);
   newrem = zws(newrem, zs);
   perm_out = zws(perm_out, zs);
-  if (blockIdx.x > 0) {
-    s1_helper(G, ldg, blk, b, S1, d, sync, (float*)vals, status, cap);
-    return;
-  }
   int* hist = (int*)(vals + r);
   unsigned char* sel = (unsigned char*)(vals + region0);
   int* sc = (int*)(sel + ((r + 15) & ~15));
   int* pick = sc + 80;                  // b positions, ascending
   uint32_t* pv = (uint32_t*)(pick + b); // their values
-  int* bl = (int*)(pv + b);             // b block indices (selection order)
-  float* s1 = (float*)(bl + b);
   const int tid = threadIdx.x, nt = blockDim.x, lane = tid & 63, wv = tid >> 6;
   PT2Q_TOPK_STAMP(0);
   for (int e = tid; e < r; e += nt) vals[e] = orderable(sim[e]);
@@ -756,20 +693,11 @@ __global__ __launch_bounds__(TOPK_THREADS) void ssr_topk_kernel(const float* sim
     rank += __shfl_xor(rank, 1);
     if (t < b && sub == 0) {
       const int j = rem[pick[t]];
-      __hip_atomic_store(&blk[rank], j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // sc1: helpers read it
+      blk[rank] = j;
       if (perm_out) perm_out[rank] = j;
     }
   }
-  (void)lane;
-  (void)bl;
-  (void)s1;
   PT2Q_TOPK_STAMP(6);
-  if (G) {  // publish the pick to the S1 helpers (every storing wave drained first)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) __hip_atomic_store(&sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  PT2Q_TOPK_STAMP(7);
 }
 
 // Sequential block (use_ssr=False: main.py:167-169, gptq.py:135-137) or "take the rest"
@@ -1221,8 +1149,7 @@ int pt2q_launch_ssr_similarity(const float* Wt, long ldw, int n, const int* rem,
   int nchunks = ceil_div(r, CHUNK);
   const unsigned nz = grp_z(grp);
   const long zs = grp ? grp->ws : 0;
-  const bool fused = cnt && n <= 16384 && n % 4 == 0 && ldw % 4 == 0 && (uintptr_t)Wt % 16 == 0 &&
-                     pt2q_tuning().wbar_fused;
+  const bool fused = cnt && n <= 16384 && n % 4 == 0 && ldw % 4 == 0 && (uintptr_t)Wt % 16 == 0;
   if ((nz > 1 || pre) && !fused) return PT2Q_E_UNSUPPORTED;  // grouped launches use the fused w-bar only
   if (fused) {
     hipLaunchKernelGGL(ssr_wbar_fused_kernel, dim3(pre ? 1 : nchunks, ceil_div(n, 256), nz), dim3(64), 0, st, Wt,
@@ -1245,7 +1172,7 @@ int pt2q_launch_ssr_similarity(const float* Wt, long ldw, int n, const int* rem,
   }
   const bool v4 = (n & 3) == 0 && (ldw & 3) == 0 && (uintptr_t)Wt % 16 == 0;
   const int S = ceil_div(n, 4096);
-  if (v4 && n > 4096 && n <= 16384 && pt2q_tuning().sim_split) {
+  if (v4 && n > 4096 && n <= 16384) {
     auto k = S == 2 ? ssr_sim_split_kernel<2> : S == 3 ? ssr_sim_split_kernel<3> : ssr_sim_split_kernel<4>;
     hipLaunchKernelGGL(k, dim3(r, 1, nz), dim3(64 * S), 0, st, Wt, ldw, n, rem, r, wn, sim, zs);
   } else {
@@ -1258,21 +1185,14 @@ int pt2q_launch_ssr_similarity(const float* Wt, long ldw, int n, const int* rem,
 }
 
 int pt2q_launch_ssr_topk(const float* sim, const int* rem, int r, int b, int* blk, int* newrem,
-                         int64_t* perm_out, hipStream_t st, const float* G, long ldg, float* S1,
-                         float* d, int* sync, int* status, const Grp* grp) {
-  if (G && b > 128) return PT2Q_E_ARG;
-  const unsigned nz = grp_z(grp);
-  if (nz > 1 && G) return PT2Q_E_UNSUPPORTED;  // grouped: S1/d are formed in the ATQ launch
+                         int64_t* perm_out, hipStream_t st, const Grp* grp) {
   if (b <= 0 || b > r || r >= 65536) return PT2Q_E_UNSUPPORTED;
-  if (G && !sync) return PT2Q_E_ARG;  // sync: 2 ints the caller zeroed before this launch
-  const int region0 = (r + 32 * TOPK_HPAD + 3) & ~3;  // >= S1_ROWS * 129 for the helpers
+  const int region0 = (r + 32 * TOPK_HPAD + 3) & ~3;
   const size_t lds = (size_t)region0 * 4 + (size_t)((r + 15) & ~15) + 80 * sizeof(int) +
                      (size_t)b * 4 * sizeof(int);
   if (lds > 160 * 1024) return PT2Q_E_UNSUPPORTED;
-  const int grid = G ? 1 + ceil_div(b, S1_ROWS) : 1;
-  hipLaunchKernelGGL(ssr_topk_kernel, dim3(grid, 1, nz), dim3(TOPK_THREADS), lds, st, sim, rem, r, b, blk,
-                     newrem, perm_out, G, ldg, S1, d, region0, sync, status,
-                     pt2q_tuning().spin_cap_short, grp ? grp->ws : 0l);
+  hipLaunchKernelGGL(ssr_topk_kernel, dim3(1, 1, grp_z(grp)), dim3(TOPK_THREADS), lds, st, sim, rem, r, b, blk,
+                     newrem, perm_out, region0, grp ? grp->ws : 0l);
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;
 }

@@ -225,8 +225,8 @@ GROUP_MAX = 16  # linears per pt2q_quantize_blocks_group call (PT2Q_GROUP_MAX)
 
 def group_supported(n: int, m: int, block_size: int, flags: int = _lib.FLAG_SSR | _lib.AGA_ACT) -> bool:
     """Whether pt2q_quantize_blocks_group takes linears of this shape (else per-linear loops):
-    the library's own answer (pt2q_quantize_blocks_group_supported), so shape limits, tuning
-    overrides and the error feedback's buffer limits are never restated here."""
+    the library's own answer (pt2q_quantize_blocks_group_supported), so shape limits and the
+    error feedback's buffer limits are never restated here."""
     return bool(_lib.lib().pt2q_quantize_blocks_group_supported(int(n), int(m), int(block_size), int(flags)))
 
 

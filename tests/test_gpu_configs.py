@@ -199,9 +199,9 @@ def test_per_channel_row_kernels_edges(pt2q, n, m, dt, tdt):
     """The per-channel block loop (block_size = m) on both row kernels of atq_pc.hip -- 5120 bf16
     columns: rows held in registers; otherwise streamed through the LDS ring (ragged last chunk
     at m = 4104 / 1000, f16 / f32 W) -- with rows that are not a multiple of the workgroup's, an
-    all-zero row, one-signed rows and int8 / fp32 codes: every output vs the oracle, bit-exact,
-    and equal to the old streaming wide kernel (PT2Q_ATQ_PC=0 is read at load, so the oracle
-    stands in for it here)."""
+    all-zero row, one-signed rows and int8 / fp32 codes: every output vs the oracle, bit-exact
+    (the oracle also stands in for the streaming wide kernel of atq.hip, which these shapes no
+    longer reach)."""
     Wd = pt2q.fill_synthetic((n, m), n + m, std=0.02)
     Wd[3] = 0.0
     Wd[5] = Wd[5].abs() + 0.01  # one-signed rows

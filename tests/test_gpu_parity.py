@@ -574,10 +574,14 @@ def test_gptq_wide_blocks_vs_oracle(pt2q, n, m, N, bs, ssr):
     assert bits_equal(host(alpha), ref["alpha"]) and bits_equal(host(mu), ref["mu"])
 
 
-@pytest.mark.parametrize("n,m,bs", [(300, 700, 128), (256, 1024, 256), (64, 200, 37)])
+@pytest.mark.parametrize(
+    "n,m,bs", [(300, 700, 128), (256, 1024, 256), (64, 200, 37), (132, 330, 100), (128, 256, 64)]
+)
 def test_error_feedback_entry_vs_oracle(pt2q, n, m, bs):
     """pt2q_error_feedback (main.py:187-214 for one block, standalone C entry) vs the oracle's
-    orc_error_feedback: bit-exact W after the update; rem in arbitrary (non-sorted) order."""
+    orc_error_feedback: bit-exact W after the update; rem in arbitrary (non-sorted) order.
+    (132, 330, 100): four K stages with a partial fourth, ragged row and column tiles, n no
+    multiple of 128; (128, 256, 64): the largest two-stage block, every tile whole."""
     rng = np.random.default_rng(n + m)
     W = synth.weights(700 + n, n, m)
     cols = rng.permutation(m)

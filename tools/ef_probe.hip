@@ -1,6 +1,7 @@
 // Dev tool: time the error-feedback kernel (ef.hip) alone on random data, with build-time
-// knock-outs from csrc/probe.hpp (-DPT2Q_PROBE=8: Wt loads / stores dropped, 16: no MFMAs,
-// 32: operand DMAs all from one chunk) to split its time.  tools/build_ef_probe.sh builds them.
+// knock-outs from csrc/probe.hpp (-DPT2Q_PROBE=8: Wt loads / stores dropped; -DPT2Q_EF2_KPROBE=1 no
+// Wt traffic, 2 operand DMAs all from one chunk, 4 no MFMAs, 8 / 16 L2-hot loads / stores) to split
+// its time.  tools/build_ef_probe.sh and tools/build_ef2_clock.sh build them.
 // usage: tools/_probe/ef_probe_<mask> [n] [nr] [bs] [reps] [part]
 #include "../snlp---tenary-post-train-quantization_amd/csrc/ef.hip"
 

@@ -10,8 +10,8 @@
 #include <functional>
 #include <vector>
 
-const Pt2qTuning& pt2q_tuning() {
-  static Pt2qTuning t;
+const Pt2qSpinCaps& pt2q_spin_caps() {
+  static Pt2qSpinCaps t;
   return t;
 }
 int pt2q_launch_gram16(const GemmDesc&, int*, hipStream_t, int*) { return PT2Q_E_UNSUPPORTED; }

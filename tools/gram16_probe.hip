@@ -9,15 +9,9 @@
 #include <cstdlib>
 #include <vector>
 
-// the library's tuning (api.hip), reduced to the Gram knobs this probe varies
-const Pt2qTuning& pt2q_tuning() {
-  static Pt2qTuning t = [] {
-    Pt2qTuning u;
-    auto gi = [](const char* k, int d) { const char* v = getenv(k); return v ? atoi(v) : d; };
-    u.gram_wide = gi("PT2Q_GRAM_WIDE", 1);
-    u.gram_super = gi("PT2Q_GRAM_SUPER", 0);
-    return u;
-  }();
+// the library's spin caps (api.hip) at their defaults
+const Pt2qSpinCaps& pt2q_spin_caps() {
+  static Pt2qSpinCaps t;
   return t;
 }
 

@@ -22,5 +22,5 @@ for _ in range(reps):
 e1.record()
 torch.cuda.synchronize()
 ms = e0.elapsed_time(e1) / reps
-print(f"stages={os.environ.get('PT2Q_GEMMX_STAGES', '2')} m={m} x{batch}: {ms:.1f} ms  "
+print(f"m={m} x{batch}: {ms:.1f} ms  "
       f"{batch * float(m) ** 3 / ms / 1e9:.1f} TF/s on m^3", flush=True)
