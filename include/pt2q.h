@@ -16,7 +16,11 @@
  *     stream, created once) and joins it back with events before the call's last kernel: to the
  *     caller it is still one ordered sequence on `stream`, and under graph capture the side
  *     stream joins the capture.  PT2Q_CHOL_LOOKAHEAD=0 keeps everything on `stream`.
- *   - Matrices are row-major with explicit leading dimensions (in elements).
+ *   - Matrices are row-major with explicit leading dimensions (in elements): any ld >= the row
+ *     length (a shorter one is PT2Q_E_ARG) and any element-aligned base, unless the entry says
+ *     otherwise -- an entry that cannot honour an ld or an alignment returns PT2Q_E_UNSUPPORTED
+ *     before launching anything.  Columns past the row length are never read into a result
+ *     and never written.
  *   - Return value: PT2Q_OK or an error code; launch-time argument errors only.  Numerical
  *     status discovered on the device (Cholesky breakdown) is written to `info_dev`; a stalled
  *     cross-workgroup wait is written to the workspace status word (PT2Q_E_STALL).
@@ -283,8 +287,8 @@ int pt2q_pack_ternary(const int8_t* T, int64_t count, uint8_t* packed, void* str
 int pt2q_unpack_ternary(const uint8_t* packed, int64_t count, int8_t* T, void* stream);
 
 /* out = ((parts[0] + parts[1]) + parts[2]) + ... + parts[nparts-1], elementwise fp32 in rank order;
- * part p starts at parts + p*stride (count floats each; count and stride multiples of 4, 16-byte
- * aligned; out may be parts[0]).  The deterministic reduction of the intra-layer split
+ * part p starts at parts + p*stride (count floats each; count and stride multiples of 4, parts and
+ * out 16-byte aligned, else PT2Q_E_UNSUPPORTED before anything is launched; out may be parts[0]).  The deterministic reduction of the intra-layer split
  * (the Gram of main.py:128 data-parallel over the N calibration rows, one partial
  * Gram per rank, folded on the destination rank in rank order) -- an all-reduce would leave the
  * order to the ring schedule. */

@@ -585,7 +585,7 @@ extern "C" int pt2q_gram_batched_upper(int batch, const void* const* X, int xdty
 extern "C" int pt2q_prepare_hessian(const float* G, int64_t ldg, int m, int64_t nsamples,
                                     float percdamp, float* H, int64_t ldh, float* damp_dev,
                                     void* stream) {
-  if (!G || !H || m <= 0 || nsamples <= 0) return PT2Q_E_ARG;
+  if (!G || !H || m <= 0 || nsamples <= 0 || ldg < m || ldh < m) return PT2Q_E_ARG;
   return pt2q_launch_prepare_hessian(G, ldg, m, nsamples, percdamp, H, ldh, damp_dev,
                                      (hipStream_t)stream);
 }
@@ -593,7 +593,7 @@ extern "C" int pt2q_prepare_hessian(const float* G, int64_t ldg, int m, int64_t 
 extern "C" int pt2q_cholesky_inverse(const float* H, int64_t ldh, int m, float* Hinv,
                                      int64_t ldhi, void* workspace, size_t workspace_bytes,
                                      int* info_dev, void* stream) {
-  if (!H || !Hinv || !info_dev || m <= 0) return PT2Q_E_ARG;
+  if (!H || !Hinv || !info_dev || m <= 0 || ldh < m || ldhi < m) return PT2Q_E_ARG;
   Carve c{(char*)workspace, workspace_bytes};
   float* U = c.take<float>((size_t)m * m);
   float* Ui = c.take<float>((size_t)m * m);
@@ -803,7 +803,7 @@ extern "C" int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n
 
 extern "C" int pt2q_s1_from_gram(const float* S, int64_t lds, int b, float* S1, float* d_dev,
                                  void* stream) {
-  if (!S || !S1 || !d_dev || b <= 0) return PT2Q_E_ARG;
+  if (!S || !S1 || !d_dev || b <= 0 || lds < b) return PT2Q_E_ARG;
   return pt2q_launch_aga_s1(1, S, lds, nullptr, b, S1, d_dev, (hipStream_t)stream);
 }
 

@@ -77,6 +77,32 @@ def test_argument_bounds_without_device(pt2q):
     assert lib.pt2q_quantize_blocks(p, 0, 64, 16, 64, 32, 0x11, p, 32, p, 64, 100, p, p, p, I8, p,
                                     None, p, 1 << 30, None) == E_ARG
     assert lib.pt2q_ssr_select(p, 63, 16, 64, p, 64, 32, p, p, None, p, 1 << 30, None) == E_ARG
+    # every other entry that takes a leading dimension: one short ld at a time, the rest valid
+    assert lib.pt2q_prepare_hessian(p, 63, 64, 100, 0.01, p, 64, p, None) == E_ARG
+    assert lib.pt2q_prepare_hessian(p, 64, 64, 100, 0.01, p, 63, p, None) == E_ARG
+    assert lib.pt2q_cholesky_inverse(p, 63, 64, p, 64, p, 1 << 30, p, None) == E_ARG
+    assert lib.pt2q_cholesky_inverse(p, 64, 64, p, 63, p, 1 << 30, p, None) == E_ARG
+    assert lib.pt2q_s1_from_gram(p, 63, 64, p, p, None) == E_ARG
+    assert lib.pt2q_s1_from_gram_batched(p, 63, 64, 2, 64 * 64, p, None) == E_ARG
+    assert lib.pt2q_s1_from_gram_batched(p, 66, 64, 2, 66 * 64 - 1, p, None) == E_ARG
+    assert lib.pt2q_s1_from_upper_batched(p, 600, 604, 2, 604 * 604, p, None) == E_ARG
+    assert lib.pt2q_s1_from_upper_batched(p, 608, 604, 2, 608 * 604 - 4, p, None) == E_ARG
+    FULL = 5
+    assert lib.pt2q_atq_stage(FULL, p, 63, 16, 64, p, p, p, 64, None, None, 100, None, p, 256, None) == E_ARG
+    assert lib.pt2q_atq_stage(FULL, p, 64, 16, 64, p, p, p, 63, None, None, 100, None, p, 256, None) == E_ARG
+
+    def ef(ldw=64, lde=32, ldhi=64):
+        return lib.pt2q_error_feedback(p, ldw, 16, 64, p, 32, p, 32, p, lde, p, ldhi, p, 1 << 30, None)
+    assert ef(ldw=63) == E_ARG
+    assert ef(lde=31) == E_ARG
+    assert ef(ldhi=63) == E_ARG
+
+    def tl(ldx=128, ldy=16):
+        return lib.pt2q_ternary_linear(p, F16, 4, ldx, 16, 128, p, p, p, p, 1, 128, None, p, F16, ldy,
+                                       p, 1 << 30, None)
+    assert tl(ldx=127) == E_ARG
+    assert tl(ldy=15) == E_ARG
+    assert lib.pt2q_ternary_pack(p, 127, 16, 128, p, 0, p, p, None) == E_ARG
 
 
 def test_workspace_sizes(pt2q):
