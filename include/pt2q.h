@@ -15,7 +15,7 @@
  *     forks part of its work onto an internal low-priority stream (one per device and caller
  *     stream, created once) and joins it back with events before the call's last kernel: to the
  *     caller it is still one ordered sequence on `stream`, and under graph capture the side
- *     stream joins the capture.  PT2Q_CHOL_LOOKAHEAD=0 keeps everything on `stream`.
+ *     stream joins the capture.
  *   - Matrices are row-major with explicit leading dimensions (in elements): any ld >= the row
  *     length (a shorter one is PT2Q_E_ARG) and any element-aligned base, unless the entry says
  *     otherwise -- an entry that cannot honour an ld or an alignment returns PT2Q_E_UNSUPPORTED
@@ -48,7 +48,8 @@ extern "C" {
 
 /* Status word.  pt2q_gram (with a workspace), pt2q_quantize_layer, pt2q_quantize_blocks and
  * pt2q_ssr_select reserve the FIRST PT2Q_STATUS_BYTES of their workspace for an int status word,
- * zeroed on the call's stream.  Kernels that wait on another workgroup's hand-off (stream-K
+ * zeroed on the call's stream (so do pt2q_cosine_similarity and pt2q_ssr_static_order, whose
+ * kernels never wait on another workgroup and leave it zero).  Kernels that wait on another workgroup's hand-off (stream-K
  * Gram partials, the in-launch S1/d and top-k hand-offs) give up after a bounded number of polls
  * (seconds) and then set a non-zero bit there instead of continuing silently: after the stream
  * completes, a non-zero word means the outputs are invalid (PT2Q_E_STALL). */
@@ -264,6 +265,26 @@ size_t pt2q_ssr_workspace_bytes(int n, int m);
 int pt2q_ssr_select(const float* W, int64_t ldw, int n, int m, const int64_t* rem, int r, int b,
                     int64_t* blk, int64_t* newrem, float* sim, void* workspace,
                     size_t workspace_bytes, void* stream);
+
+/* compute_cosine_similarity_matrix (reorder.py:15-33, paper Eq. 15): S = WnᵀWn (m x m fp32, full
+ * symmetric) with Wn = W / clamp(column norms, 1e-8), W n x m row-major of type wdtype.  Each norm
+ * is the square root of a k-ascending fmaf chain over the column, the division is correctly
+ * rounded and S is pt2q_gram's f32 chain on Wn, so S equals the oracle's Gram of
+ * the numpy-normalised W bit for bit. */
+size_t pt2q_cosine_similarity_workspace_bytes(int n, int m);
+int pt2q_cosine_similarity(const void* W, int wdtype, int64_t ldw, int n, int m, float* S, int64_t lds,
+                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* The greedy column order of get_initial_reorder_indices (reorder.py:81-104) on a given symmetric
+ * S (m x m): perm[0] is the first maximum of the sequential row sums (pt2q_s1_from_gram's), perm[t]
+ * the unselected column with the largest running sum of S over the columns chosen so far (one
+ * fp32 add per step, in selection order), equal sums to the lowest index; inv_perm (nullable)
+ * receives the inverse, inv_perm[perm[t]] = t.  The reference takes the mean, a monotone image of
+ * that sum, and leaves ties to argmax.  One workgroup, one launch; m <= 16384, else
+ * PT2Q_E_UNSUPPORTED before anything is launched. */
+size_t pt2q_ssr_static_order_workspace_bytes(int m);
+int pt2q_ssr_static_order(const float* S, int64_t lds, int m, int64_t* perm, int64_t* inv_perm,
+                          void* workspace, size_t workspace_bytes, void* stream);
 
 /* One block's GPTQ error feedback, in place (main.py:187-214, gptq.py:158-186):
  *   C = Hinv[blk][:, rem] / clamp(diag(Hinv)[blk], 1e-8);  W[:, rem] -= E @ C

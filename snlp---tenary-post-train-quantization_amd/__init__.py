@@ -2,7 +2,9 @@
 
 Drop-in for the reference's hot-path surface:
     AsymmetricTernaryQuantizer, compute_quantization_error, compute_output_error  (quantizer.py)
-    compute_column_similarity_to_mean, select_next_block_ssr                      (reorder.py)
+    compute_column_similarity_to_mean, select_next_block_ssr,
+    compute_cosine_similarity_matrix, get_initial_reorder_indices, SSRReorderer,
+    apply_permutation, apply_permutation_to_input, compute_block_variance         (reorder.py)
     GPTQ, GPTQQuantizer                                                            (gptq.py)
     PT2LLMQuantizer.quantize_layer                                                 (main.py)
     pack_ternary, unpack_ternary, save/load_quantized_model,
@@ -12,7 +14,9 @@ All compute runs in libpt2q.so (HIP, gfx950); importing fails loudly if it is no
 """
 from . import _lib
 from .quantizer import AsymmetricTernaryQuantizer, compute_output_error, compute_quantization_error
-from .reorder import compute_column_similarity_to_mean, select_next_block_ssr
+from .reorder import (SSRReorderer, apply_permutation, apply_permutation_to_input, compute_block_variance,
+                      compute_column_similarity_to_mean, compute_cosine_similarity_matrix,
+                      get_initial_reorder_indices, select_next_block_ssr)
 from .gptq import GPTQ, GPTQQuantizer
 from .pt2llm import PT2LLMQuantizer
 from .calibration import (GramAccumulator, GramCapture, find_linear_layers, get_llm_layers,
@@ -35,5 +39,7 @@ __all__ = [
     "GramCapture", "find_linear_layers", "get_llm_layers", "quantize_decoder_layer",
     "TernaryLinear", "replace_linear_with_ternary", "save_quantized_model", "load_quantized_model",
     "UnitRun", "UnitWorkspace", "quantize_unit", "compute_bits_per_weight", "error_feedback",
-    "UnitPipeline", "sum_partials", "evaluate_perplexity",
+    "UnitPipeline", "sum_partials", "evaluate_perplexity", "compute_cosine_similarity_matrix",
+    "get_initial_reorder_indices", "SSRReorderer", "apply_permutation", "apply_permutation_to_input",
+    "compute_block_variance",
 ]

@@ -76,6 +76,10 @@ _SIGS = {
     "pt2q_s1_from_gram_batched": (I, [P, I64, I, I, I64, P, P]),
     "pt2q_s1_from_upper_batched": (I, [P, I64, I, I, I64, P, P]),
     "pt2q_ssr_select": (I, [P, I64, I, I, P, I, I, P, P, P, P, SZ, P]),
+    "pt2q_cosine_similarity_workspace_bytes": (SZ, [I, I]),
+    "pt2q_cosine_similarity": (I, [P, I, I64, I, I, P, I64, P, SZ, P]),
+    "pt2q_ssr_static_order_workspace_bytes": (SZ, [I]),
+    "pt2q_ssr_static_order": (I, [P, I64, I, P, P, P, SZ, P]),
     "pt2q_dequantize": (I, [P, P, P, I, P, I, I, I, P, P]),
     "pt2q_error_feedback_workspace_bytes": (SZ, [I, I, I]),
     "pt2q_error_feedback": (I, [P, I64, I, I, P, I, P, I, P, I64, P, I64, P, SZ, P]),

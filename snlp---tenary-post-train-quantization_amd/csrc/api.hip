@@ -864,6 +864,67 @@ extern "C" int pt2q_ssr_select(const float* W, int64_t ldw, int n, int m, const 
   return PT2Q_OK;
 }
 
+// ---- static reorder (reorder.py:15-33, :81-104)
+extern "C" size_t pt2q_cosine_similarity_workspace_bytes(int n, int m) {
+  if (n <= 0 || m <= 0) return 0;
+  Carve c{nullptr, 0};
+  c.dry = true;
+  c.take<int>(PT2Q_STATUS_BYTES / sizeof(int));
+  c.take<float>((size_t)m);                          // column norms
+  c.take<float>((size_t)n * round_up(m, 4));         // Wn
+  return c.used;
+}
+
+extern "C" int pt2q_cosine_similarity(const void* W, int wdtype, int64_t ldw, int n, int m, float* S,
+                                      int64_t lds, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!W || !S || n <= 0 || m <= 0 || !dtype_ok(wdtype) || ldw < m || lds < m) return PT2Q_E_ARG;
+  if (!workspace || workspace_bytes < pt2q_cosine_similarity_workspace_bytes(n, m)) return PT2Q_E_WORKSPACE;
+  Carve c{(char*)workspace, workspace_bytes};
+  int rc;
+  take_status(c, st, rc);  // reserved (every Gram tile is one chain: nothing waits on another workgroup)
+  if (rc != PT2Q_OK) return rc;
+  const long ldn = round_up(m, 4);  // 16-byte rows: the Gram's vector loads apply when m % 4 == 0
+  float* nrm = c.take<float>((size_t)m);
+  float* Wn = c.take<float>((size_t)n * ldn);
+  if (!c.ok) return PT2Q_E_WORKSPACE;
+  if ((rc = pt2q_launch_colnorm_normalize(W, wdtype, ldw, n, m, nrm, Wn, ldn, st)) != PT2Q_OK) return rc;
+  GemmDesc g{};
+  g.M = m; g.N = m; g.K = n;
+  g.A = Wn; g.lda = ldn; g.a_layout = LAY_KMAJOR;
+  g.B = Wn; g.ldb = ldn; g.b_layout = LAY_KMAJOR;
+  g.in_dtype = PT2Q_F32;
+  g.C = S; g.ldc = lds;
+  g.mode = GEMM_STORE;
+  g.upper = 1; g.mirror = 1;
+  return pt2q_launch_gram(g, nullptr, st);
+}
+
+extern "C" size_t pt2q_ssr_static_order_workspace_bytes(int m) {
+  if (m <= 0) return 0;
+  Carve c{nullptr, 0};
+  c.dry = true;
+  c.take<int>(PT2Q_STATUS_BYTES / sizeof(int));
+  c.take<float>((size_t)m + 1);  // row sums, then their total (pt2q_launch_s1_batched's layout)
+  return c.used;
+}
+
+extern "C" int pt2q_ssr_static_order(const float* S, int64_t lds, int m, int64_t* perm, int64_t* inv_perm,
+                                     void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!S || !perm || m <= 0 || lds < m) return PT2Q_E_ARG;
+  if (m > PT2Q_STATIC_ORDER_MAX) return PT2Q_E_UNSUPPORTED;
+  if (!workspace || workspace_bytes < pt2q_ssr_static_order_workspace_bytes(m)) return PT2Q_E_WORKSPACE;
+  Carve c{(char*)workspace, workspace_bytes};
+  int rc;
+  take_status(c, st, rc);  // reserved (one workgroup: nothing waits on another)
+  if (rc != PT2Q_OK) return rc;
+  float* S1d = c.take<float>((size_t)m + 1);
+  if (!c.ok) return PT2Q_E_WORKSPACE;
+  if ((rc = pt2q_launch_s1_batched(S, lds, m, 1, 0, S1d, st)) != PT2Q_OK) return rc;
+  return pt2q_launch_greedy_order(S, lds, m, S1d, perm, inv_perm, st);
+}
+
 // ---- standalone error feedback (main.py:187-214 / gptq.py:158-186 for one block)
 extern "C" size_t pt2q_error_feedback_workspace_bytes(int n, int m, int bs) {
   if (n <= 0 || m <= 0 || bs <= 0) return 0;

@@ -89,6 +89,15 @@ int pt2q_launch_ef_coeffs(const float* Hinv, long ldh, const int* blk, int bs, c
                           int nr, float* C, long ldc, hipStream_t st);
 size_t pt2q_ssr_scratch_floats(int n, int m);
 
+// ---- static reorder (reorder_static.hip)
+// nrm[j] = clamp(sqrt(fmaf chain of column j), 1e-8) and Wn = W / nrm (fp32, ld ldn >= m)
+int pt2q_launch_colnorm_normalize(const void* W, int wdtype, long ldw, int n, int m, float* nrm, float* Wn,
+                                  long ldn, hipStream_t st);
+// the greedy order on a symmetric S given its sequential row sums; one workgroup, m <= the limit
+constexpr int PT2Q_STATIC_ORDER_MAX = 16384;
+int pt2q_launch_greedy_order(const float* S, long lds, int m, const float* rowsum, int64_t* perm,
+                             int64_t* inv_perm, hipStream_t st);
+
 // ---- GEMM (gemm.hip)
 enum GemmMode { GEMM_STORE = 0, GEMM_ADD = 1, GEMM_SUB = 2, GEMM_CHAIN_NEG = 3, GEMM_CHAIN_POS = 4 };
 enum GemmLayout { LAY_KMAJOR = 0, LAY_ROWMAJOR = 1 };
