@@ -48,8 +48,8 @@ extern "C" {
 
 /* Status word.  pt2q_gram (with a workspace), pt2q_quantize_layer, pt2q_quantize_blocks and
  * pt2q_ssr_select reserve the FIRST PT2Q_STATUS_BYTES of their workspace for an int status word,
- * zeroed on the call's stream (so do pt2q_cosine_similarity and pt2q_ssr_static_order, whose
- * kernels never wait on another workgroup and leave it zero).  Kernels that wait on another workgroup's hand-off (stream-K
+ * zeroed on the call's stream (so do pt2q_cosine_similarity, pt2q_ssr_static_order, pt2q_quadform_rows
+ * and pt2q_layer_report, whose kernels never wait on another workgroup and leave it zero).  Kernels that wait on another workgroup's hand-off (stream-K
  * Gram partials, the in-launch S1/d and top-k hand-offs) give up after a bounded number of polls
  * (seconds) and then set a non-zero bit there instead of continuing silently: after the stream
  * completes, a non-zero word means the outputs are invalid (PT2Q_E_STALL). */
@@ -285,6 +285,42 @@ int pt2q_cosine_similarity(const void* W, int wdtype, int64_t ldw, int n, int m,
 size_t pt2q_ssr_static_order_workspace_bytes(int m);
 int pt2q_ssr_static_order(const float* S, int64_t lds, int m, int64_t* perm, int64_t* inv_perm,
                           void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---- Per-layer quantization error report from the Gram (no reference counterpart in this form:
+ * compute_quantization_error / compute_output_error, quantizer.py:296-306, need W_c and the whole
+ * X; the model flow holds only G = XᵀX).  Arithmetic: DESIGN.md §3 "Layer report" -- bit-defined,
+ * restated in numpy by tests/report_ref.py. */
+#define PT2Q_REPORT_REF 0x1   /* also ey[i] = w_i G w_iᵀ, the reference energy ‖w_i Xᵀ‖² */
+
+/* q[i] = a_i G a_iᵀ for the rows of A (rows x m, row-major, adtype fp32 / fp16 / bf16 upcast
+ * exactly): with A = W - W_c and G = XᵀX the per-row terms of compute_output_error
+ * (quantizer.py:301-306: ‖(W - W_c) Xᵀ‖²_F), without X.  G m x m fp32 with any ldg >= m and any
+ * element-aligned base (16-byte aligned with ldg % 4 == 0 and m % 4 == 0 takes the fast operand
+ * path); it is read as stored, all of it: an upper-only Gram (pt2q_gram_batched_upper) is NOT
+ * accepted.  P = A G is a k-ascending fmaf chain per entry (f32 MFMA) that never reaches memory;
+ * q[i] is the ROWTREE sum of RN(P_ij a_ij).  q (nullable): rows floats; total (nullable): one
+ * float, ROWTREE of q.  workspace: pt2q_quadform_rows_workspace_bytes(rows, m). */
+size_t pt2q_quadform_rows_workspace_bytes(int rows, int m);
+int pt2q_quadform_rows(const void* A, int adtype, int64_t lda, int rows, int m, const float* G,
+                       int64_t ldg, float* q, float* total, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* The report of one quantized layer: D = W - W_hat with W_hat = pt2q_dequantize(alpha, mu, T, perm, b)
+ * formed on the fly (W n x m of wdtype; alpha, mu n x B fp32 packed; T n x m codes in ORIGINAL
+ * column order, int8 or fp32, leading dim ldt; perm m int64 or NULL = identity), then
+ *   ew[i] = Σ_j d_ij²      (compute_quantization_error, quantizer.py:296-298, per row)
+ *   ex[i] = d_i G d_iᵀ     (compute_output_error, quantizer.py:301-306, per row, from the Gram)
+ *   ey[i] = w_i G w_iᵀ     (flags & PT2Q_REPORT_REF: the energy the output error is relative to)
+ *   totals[0..2] = their ROWTREE sums (an output not computed gives 0).
+ * G = NULL gives ew only.  ew, ex, ey (n floats each) and totals (3 floats) are nullable.  The D
+ * and W rows share one launch of the fused kernel (2n rows against the same G panels).  G as for
+ * pt2q_quadform_rows.  workspace: pt2q_layer_report_workspace_bytes(n, m, flags). */
+size_t pt2q_layer_report_workspace_bytes(int n, int m, int flags);
+int pt2q_layer_report(const void* W, int wdtype, int64_t ldw, int n, int m, int b,
+                      const float* alpha, const float* mu, const void* T, int tdtype, int64_t ldt,
+                      const int64_t* perm, const float* G, int64_t ldg, int flags,
+                      float* ew, float* ex, float* ey, float* totals,
+                      void* workspace, size_t workspace_bytes, void* stream);
 
 /* One block's GPTQ error feedback, in place (main.py:187-214, gptq.py:158-186):
  *   C = Hinv[blk][:, rem] / clamp(diag(Hinv)[blk], 1e-8);  W[:, rem] -= E @ C

@@ -2,6 +2,7 @@
 
 Drop-in for the reference's hot-path surface:
     AsymmetricTernaryQuantizer, compute_quantization_error, compute_output_error  (quantizer.py)
+    compute_output_error_from_gram, quadform_rows, layer_report   (the same metrics from the Gram)
     compute_column_similarity_to_mean, select_next_block_ssr,
     compute_cosine_similarity_matrix, get_initial_reorder_indices, SSRReorderer,
     apply_permutation, apply_permutation_to_input, compute_block_variance         (reorder.py)
@@ -13,7 +14,8 @@ Drop-in for the reference's hot-path surface:
 All compute runs in libpt2q.so (HIP, gfx950); importing fails loudly if it is not built.
 """
 from . import _lib
-from .quantizer import AsymmetricTernaryQuantizer, compute_output_error, compute_quantization_error
+from .quantizer import (AsymmetricTernaryQuantizer, compute_output_error, compute_output_error_from_gram,
+                        compute_quantization_error, quadform_rows)
 from .reorder import (SSRReorderer, apply_permutation, apply_permutation_to_input, compute_block_variance,
                       compute_column_similarity_to_mean, compute_cosine_similarity_matrix,
                       get_initial_reorder_indices, select_next_block_ssr)
@@ -27,7 +29,7 @@ from .evaluation import evaluate_perplexity
 from .engine import (LayerGraph, LayerOutput, LayerWorkspace, UnitRun, UnitWorkspace, cholesky_inverse,
                      dequantize, error_feedback, fill_synthetic, gram, hessian_inverse, pack_ternary, prepare_hessian,
                      quantize_blocks, quantize_layer, quantize_shared, quantize_unit, unpack_ternary,
-                     UnitPipeline, sum_partials)
+                     UnitPipeline, sum_partials, LayerReport, layer_report)
 
 __version__ = "0.1.0"
 __all__ = [
@@ -41,5 +43,5 @@ __all__ = [
     "UnitRun", "UnitWorkspace", "quantize_unit", "compute_bits_per_weight", "error_feedback",
     "UnitPipeline", "sum_partials", "evaluate_perplexity", "compute_cosine_similarity_matrix",
     "get_initial_reorder_indices", "SSRReorderer", "apply_permutation", "apply_permutation_to_input",
-    "compute_block_variance",
+    "compute_block_variance", "LayerReport", "layer_report", "quadform_rows", "compute_output_error_from_gram",
 ]

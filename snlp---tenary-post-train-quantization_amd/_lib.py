@@ -21,6 +21,7 @@ FLAG_SSR = 0x1
 FLAG_S1_GIVEN = 0x2
 AGA_NONE, AGA_ACT, AGA_HESS = 0x0, 0x10, 0x20
 AGA_MASK = 0x30
+REPORT_REF = 0x1
 STAGE_INIT, STAGE_GRID, STAGE_ROUND, STAGE_ITF, STAGE_AGA, STAGE_FULL = range(6)
 # stage-timer classes (pt2q_stage_timing, include/pt2q.h PT2Q_TIMER_*)
 TIMERS = ("setup", "ssr", "atq", "ef", "out", "gram", "inverse")
@@ -80,6 +81,10 @@ _SIGS = {
     "pt2q_cosine_similarity": (I, [P, I, I64, I, I, P, I64, P, SZ, P]),
     "pt2q_ssr_static_order_workspace_bytes": (SZ, [I]),
     "pt2q_ssr_static_order": (I, [P, I64, I, P, P, P, SZ, P]),
+    "pt2q_quadform_rows_workspace_bytes": (SZ, [I, I]),
+    "pt2q_quadform_rows": (I, [P, I, I64, I, I, P, I64, P, P, P, SZ, P]),
+    "pt2q_layer_report_workspace_bytes": (SZ, [I, I, I]),
+    "pt2q_layer_report": (I, [P, I, I64, I, I, I, P, P, P, I, I64, P, P, I64, I, P, P, P, P, P, SZ, P]),
     "pt2q_dequantize": (I, [P, P, P, I, P, I, I, I, P, P]),
     "pt2q_error_feedback_workspace_bytes": (SZ, [I, I, I]),
     "pt2q_error_feedback": (I, [P, I64, I, I, P, I, P, I, P, I64, P, I64, P, SZ, P]),

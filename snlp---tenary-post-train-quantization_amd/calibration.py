@@ -292,7 +292,8 @@ def propagate_layer(layer: nn.Module, inputs):
 def quantize_decoder_layer(layer: nn.Module, run_forward, block_size: int = 128,
                            use_ssr: bool = True, percdamp: float = 0.01, layer_idx: int = 0,
                            writeback: str = "reference", device=None,
-                           pipeline: Optional["engine.UnitPipeline"] = None, grams_first=None):
+                           pipeline: Optional["engine.UnitPipeline"] = None, grams_first=None,
+                           report: Optional[dict] = None):
     """One iteration of main.py:258-303 for decoder layer `layer`.
 
     run_forward(capture) must run the calibration forwards (calling capture.next_pass() between
@@ -304,7 +305,17 @@ def quantize_decoder_layer(layer: nn.Module, run_forward, block_size: int = 128,
     results identical to the one-after-another order.
     With a sharding.GramsFirst (`grams_first`, built on such a pipeline) the captured Grams go into
     its packed slots instead: the layer's Hessian inverses run batched per width and the block
-    loops grouped by shape on the lanes (q/k/v/o, gate/up) -- bit-identical again."""
+    loops grouped by shape on the lanes (q/k/v/o, gate/up) -- bit-identical again.
+    report: a dict that receives {"layer_<i>.<name>": {weight_error, output_error,
+    reference_energy, relative_output_error, nsamples}} (host floats, engine.layer_report): each
+    linear's error is computed after its unit's finish() and BEFORE its write-back, from the
+    original weights (a linear's weight is replaced only in its own turn of the loop below), the
+    engine's fp32 grids and its group's full raw Gram acc.G.  acc.G is complete and valid there
+    under both schedules: GramAccumulator owns that buffer and nothing writes it after the capture
+    -- grams_first.set_gram copies it into the packed slot (the upper-only Grams of
+    sharding.flush live in those slots only), and UnitPipeline.run reads it in place.  The
+    reports run on the caller's stream after finish() has joined the lanes; the returned params
+    and the written-back weights are those of report=None."""
     linears = find_linear_layers(layer)
     cap = GramCapture(linears, device)
     with cap:
@@ -329,11 +340,14 @@ def quantize_decoder_layer(layer: nn.Module, run_forward, block_size: int = 128,
         else:
             issued.append((names, engine.quantize_shared(Ws, acc.G, acc.nsamples, block_size, use_ssr,
                                                          percdamp)))
-    for names, outs in issued:
+    for (acc, _), (names, outs) in zip(groups, issued):
         if pipeline is not None or grams_first is not None:
             outs = outs.finish()
         for nm, out in zip(names, outs):
             lin = linears[nm]
+            if report is not None:
+                rep = engine.layer_report(lin.weight.data.to(acc.device), out, acc.G, block_size)
+                report[f"layer_{layer_idx}.{nm}"] = rep.as_dict(acc.nsamples)
             dt = lin.weight.dtype
             params = {"alpha": out.alpha.to(dt), "mu": out.mu.to(dt), "T": out.T, "perm": out.perm}
             results[f"layer_{layer_idx}.{nm}"] = params

@@ -984,3 +984,108 @@ extern "C" int pt2q_error_feedback(float* W, int64_t ldw, int n, int m, const in
   if (rc != PT2Q_OK) return rc;
   return pt2q_launch_transpose_f32(Wt, ldW, m, n, W, ldw, st);
 }
+
+// ---- per-layer error report from the Gram (quantizer.py:296-306 in Gram form; layer_report.hip)
+namespace {
+
+struct ReportCarve {
+  int* blockof;
+  float *At, *partw, *part, *rows, *tsc;
+  long npad, R;
+};
+
+// rows: the A operand's data rows (n, or n D rows and n W rows at offset npad); `codes`: the
+// residual path's block table and ew partials
+ReportCarve report_carve(Carve& c, int n, int m, bool two, bool codes) {
+  ReportCarve r{};
+  r.npad = round_up(n, 128);
+  r.R = two ? 2 * r.npad : r.npad;
+  const size_t nch = (size_t)ceil_div(m, 32);
+  if (codes) r.blockof = c.take<int>((size_t)m);
+  r.At = c.take<float>((size_t)m * r.R);
+  if (codes) r.partw = c.take<float>(nch * r.npad);
+  r.part = c.take<float>(nch * r.R);
+  r.rows = c.take<float>((size_t)3 * n);                      // stand-ins for NULL per-row outputs
+  r.tsc = c.take<float>((size_t)3 * ceil_div(n, 32) + 4);     // totals scratch
+  return r;
+}
+
+}  // namespace
+
+extern "C" size_t pt2q_quadform_rows_workspace_bytes(int rows, int m) {
+  if (rows <= 0 || m <= 0) return 0;
+  Carve c{nullptr, 0};
+  c.dry = true;
+  c.take<int>(PT2Q_STATUS_BYTES / sizeof(int));
+  report_carve(c, rows, m, false, false);
+  return c.used;
+}
+
+extern "C" int pt2q_quadform_rows(const void* A, int adtype, int64_t lda, int rows, int m, const float* G,
+                                  int64_t ldg, float* q, float* total, void* workspace, size_t workspace_bytes,
+                                  void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!A || !G || rows <= 0 || m <= 0 || !dtype_ok(adtype) || lda < m || ldg < m) return PT2Q_E_ARG;
+  if (!workspace || workspace_bytes < pt2q_quadform_rows_workspace_bytes(rows, m)) return PT2Q_E_WORKSPACE;
+  Carve c{(char*)workspace, workspace_bytes};
+  int rc;
+  take_status(c, st, rc);  // reserved (nothing in this call waits on another workgroup)
+  if (rc != PT2Q_OK) return rc;
+  const ReportCarve w = report_carve(c, rows, m, false, false);
+  if (!c.ok) return PT2Q_E_WORKSPACE;
+  float* qv = q ? q : w.rows;
+  if ((rc = pt2q_launch_report_residual(2, A, adtype, lda, rows, m, nullptr, PT2Q_I8, 0, nullptr, nullptr, 1,
+                                        nullptr, w.At, w.R, w.R, 0, nullptr, 0, st)) != PT2Q_OK)
+    return rc;
+  if ((rc = pt2q_launch_quadform_rows(w.At, w.R, w.R, m, G, ldg, w.part, w.R, st)) != PT2Q_OK) return rc;
+  if ((rc = pt2q_launch_rowtree_finish(w.part, w.R, m, 0, rows, qv, st)) != PT2Q_OK) return rc;
+  if (total) return pt2q_launch_rowtree_totals(qv, nullptr, nullptr, 1, rows, w.tsc, total, st);
+  return PT2Q_OK;
+}
+
+extern "C" size_t pt2q_layer_report_workspace_bytes(int n, int m, int flags) {
+  if (n <= 0 || m <= 0) return 0;
+  Carve c{nullptr, 0};
+  c.dry = true;
+  c.take<int>(PT2Q_STATUS_BYTES / sizeof(int));
+  report_carve(c, n, m, (flags & PT2Q_REPORT_REF) != 0, true);
+  return c.used;
+}
+
+extern "C" int pt2q_layer_report(const void* W, int wdtype, int64_t ldw, int n, int m, int b, const float* alpha,
+                                 const float* mu, const void* T, int tdtype, int64_t ldt, const int64_t* perm,
+                                 const float* G, int64_t ldg, int flags, float* ew, float* ex, float* ey,
+                                 float* totals, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!W || !T || !alpha || !mu || n <= 0 || m <= 0 || b <= 0 || !dtype_ok(wdtype) ||
+      (tdtype != PT2Q_I8 && tdtype != PT2Q_F32) || ldw < m || ldt < m || (G && ldg < m) ||
+      (flags & ~PT2Q_REPORT_REF))
+    return PT2Q_E_ARG;
+  if (!workspace || workspace_bytes < pt2q_layer_report_workspace_bytes(n, m, flags)) return PT2Q_E_WORKSPACE;
+  Carve c{(char*)workspace, workspace_bytes};
+  int rc;
+  take_status(c, st, rc);  // reserved (nothing in this call waits on another workgroup)
+  if (rc != PT2Q_OK) return rc;
+  const bool ref = (flags & PT2Q_REPORT_REF) && G;  // ey needs the Gram
+  // the carve is the size function's (flags alone); without G the W half stays unused
+  const ReportCarve w = report_carve(c, n, m, (flags & PT2Q_REPORT_REF) != 0, true);
+  if (!c.ok) return PT2Q_E_WORKSPACE;
+  const long R = ref ? 2 * w.npad : w.npad;
+  const int B = (b < m) ? ceil_div(m, b) : 1, bb = (b < m) ? b : m;  // as pt2q_dequantize
+  float* ewv = ew ? ew : w.rows;
+  float* exv = ex ? ex : w.rows + n;
+  float* eyv = ey ? ey : w.rows + 2 * (size_t)n;
+  if ((rc = pt2q_launch_report_blockof(perm, m, bb, w.blockof, st)) != PT2Q_OK) return rc;
+  if ((rc = pt2q_launch_report_residual(ref ? 1 : 0, W, wdtype, ldw, n, m, T, tdtype, ldt, alpha, mu, B, w.blockof,
+                                        w.At, R, w.npad, w.npad, w.partw, w.npad, st)) != PT2Q_OK)
+    return rc;
+  if ((rc = pt2q_launch_rowtree_finish(w.partw, w.npad, m, 0, n, ewv, st)) != PT2Q_OK) return rc;
+  if (G) {
+    if ((rc = pt2q_launch_quadform_rows(w.At, R, R, m, G, ldg, w.part, R, st)) != PT2Q_OK) return rc;
+    if ((rc = pt2q_launch_rowtree_finish(w.part, R, m, 0, n, exv, st)) != PT2Q_OK) return rc;
+    if (ref && (rc = pt2q_launch_rowtree_finish(w.part, R, m, w.npad, n, eyv, st)) != PT2Q_OK) return rc;
+  }
+  if (totals)
+    return pt2q_launch_rowtree_totals(ewv, G ? exv : nullptr, ref ? eyv : nullptr, 3, n, w.tsc, totals, st);
+  return PT2Q_OK;
+}

@@ -98,6 +98,26 @@ constexpr int PT2Q_STATIC_ORDER_MAX = 16384;
 int pt2q_launch_greedy_order(const float* S, long lds, int m, const float* rowsum, int64_t* perm,
                              int64_t* inv_perm, hipStream_t st);
 
+// ---- layer report (layer_report.hip; DESIGN.md §3 "Layer report")
+// blockof[c] = (position of column c in perm) / bb (perm nullable: identity); m ints
+int pt2q_launch_report_blockof(const int64_t* perm, int m, int bb, int* blockof, hipStream_t st);
+// mode 0: the residual D = W - dequantised codes, feature-major into Dt (m x ldd, rows [0, rows),
+// rows >= n zero; rows % 64 == 0) and the ew chunk partials partw[chunk * ldp + row]; mode 1: also
+// W itself at row offset woff of Dt; mode 2: W only (no codes, no partials)
+int pt2q_launch_report_residual(int mode, const void* W, int wdtype, long ldw, int n, int m, const void* T,
+                                int tdtype, long ldt, const float* alpha, const float* mu, int B,
+                                const int* blockof, float* Dt, long ldd, long rows, long woff, float* partw,
+                                long ldp, hipStream_t st);
+// part[chunk * ldp + i] = the 32-column chunk partials of Σ_j RN(P_ij a_ij), P = A G the k-ascending
+// chain, for the R rows (R % 128 == 0) of the K-major A = At (m x lda); any G base and ldg
+int pt2q_launch_quadform_rows(const float* At, long lda, long R, int m, const float* G, long ldg, float* part,
+                              long ldp, hipStream_t st);
+// out[i] = partials of row row0 + i over the ceil(m / 32) chunks, ascending
+int pt2q_launch_rowtree_finish(const float* part, long ldp, int m, long row0, int n, float* out, hipStream_t st);
+// totals[v] = ROWTREE of the length-n vector v (v < count <= 3; NULL vector: 0); scratch: 3 ceil(n / 32) floats
+int pt2q_launch_rowtree_totals(const float* v0, const float* v1, const float* v2, int count, int n, float* scratch,
+                               float* totals, hipStream_t st);
+
 // ---- GEMM (gemm.hip)
 enum GemmMode { GEMM_STORE = 0, GEMM_ADD = 1, GEMM_SUB = 2, GEMM_CHAIN_NEG = 3, GEMM_CHAIN_POS = 4 };
 enum GemmLayout { LAY_KMAJOR = 0, LAY_ROWMAJOR = 1 };

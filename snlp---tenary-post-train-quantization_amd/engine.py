@@ -34,6 +34,7 @@ class LayerOutput:
     perm: torch.Tensor    # m int64
     iters: torch.Tensor   # B int32 (ITF iterations per block)
     spd: bool = True
+    report: Optional["LayerReport"] = None  # quantize_unit(report=True)
 
 
 def gram(X: torch.Tensor, G: Optional[torch.Tensor] = None, accumulate=False,
@@ -440,14 +441,19 @@ class UnitRun:
 def quantize_unit(Ws, X: Optional[torch.Tensor] = None, G: Optional[torch.Tensor] = None,
                   nsamples: Optional[int] = None, block_size: int = 128, use_ssr: bool = True,
                   percdamp: float = 0.01, max_iter: int = 100, t_dtype=torch.int8,
-                  workspace: Optional[UnitWorkspace] = None, defer: bool = False):
+                  workspace: Optional[UnitWorkspace] = None, defer: bool = False, report: bool = False):
     """One work unit of the model loop (main.py:289-299 for linears that read the same input:
     q/k/v, gate/up, or a single linear): Gram of X (or a given raw Gram G over `nsamples` rows),
     damping, Cholesky inverse, then each weight's block loop, all stream-ordered with NO host
     synchronisation.  Results are bit-identical to quantize_layer(W, X) per linear.
 
     defer=False reads the status once at the end and returns [LayerOutput]; defer=True returns a
-    UnitRun whose finish() does that read later (a model loop checks once per step)."""
+    UnitRun whose finish() does that read later (a model loop checks once per step).
+    report=True (not with defer): after the status read, each output's `.report` is the
+    LayerReport of its weight against the unit's raw Gram (layer_report); the outputs themselves
+    and the launches before them are those of report=False."""
+    if report and defer:
+        raise ValueError("quantize_unit: report=True needs the finished outputs (defer=False)")
     Ws = [_float_input(W) for W in Ws]
     m = Ws[0].shape[1]
     dev = Ws[0].device
@@ -467,7 +473,13 @@ def quantize_unit(Ws, X: Optional[torch.Tensor] = None, G: Optional[torch.Tensor
         Gm = G.contiguous().float()
     run = _unit_tail(Ws, Gm, int(nsamples), ws, statuses, X, G, block_size, use_ssr, percdamp, max_iter,
                      t_dtype)
-    return run if defer else run.finish()
+    if defer:
+        return run
+    outs = run.finish()
+    if report:  # Gm: the workspace's Gram (nothing has reused it) or the caller's
+        for W, o in zip(Ws, outs):
+            o.report = layer_report(W, o, Gm, block_size)
+    return outs
 
 
 def _unit_tail(Ws, Gm, nsamples, ws, statuses, X, G, block_size, use_ssr, percdamp, max_iter, t_dtype,
@@ -766,6 +778,107 @@ def dequantize(alpha, mu, T, perm, block_size):
                                           int(block_size), _lib.ptr(out), _lib.stream_of(dev)),
                "pt2q_dequantize")
     return out
+
+
+@dataclass
+class LayerReport:
+    """Per-row quantization errors of one layer from its raw Gram (pt2q_layer_report): device fp32
+    vectors and their three ROWTREE totals; the host properties read the totals with one copy."""
+    ew: torch.Tensor                # n: Σ_j (w_ij - ŵ_ij)²        (compute_quantization_error per row)
+    ex: Optional[torch.Tensor]      # n: d_i G d_iᵀ = ‖d_i Xᵀ‖²    (compute_output_error per row)
+    ey: Optional[torch.Tensor]      # n: w_i G w_iᵀ = ‖w_i Xᵀ‖²    (reference energy)
+    totals: torch.Tensor            # 3: their sums (0 where not computed)
+    _host: Optional[list] = None
+
+    def _totals(self):
+        if self._host is None:
+            self._host = self.totals.cpu().tolist()
+        return self._host
+
+    @property
+    def weight_error(self) -> float:
+        return self._totals()[0]
+
+    @property
+    def output_error(self) -> Optional[float]:
+        return self._totals()[1] if self.ex is not None else None
+
+    @property
+    def reference_energy(self) -> Optional[float]:
+        return self._totals()[2] if self.ey is not None else None
+
+    @property
+    def relative_output_error(self) -> Optional[float]:
+        if self.ex is None or self.ey is None:
+            return None
+        t = self._totals()
+        return t[1] / t[2] if t[2] != 0 else float("nan")
+
+    def as_dict(self, nsamples: Optional[int] = None) -> dict:
+        """Host floats (one device read)."""
+        return {"weight_error": self.weight_error, "output_error": self.output_error,
+                "reference_energy": self.reference_energy,
+                "relative_output_error": self.relative_output_error, "nsamples": nsamples}
+
+
+def layer_report(W: torch.Tensor, out, G: Optional[torch.Tensor], block_size: int,
+                 reference: bool = True) -> LayerReport:
+    """The quantization error of one layer without its activations (quantizer.py:296-306 in Gram
+    form): with D = W - dequantize(out) and the raw Gram G = XᵀX (m x m fp32, the FULL symmetric
+    matrix -- not pt2q_gram_batched_upper's upper-only form),
+        ew[i] = Σ_j d_ij²,  ex[i] = d_i G d_iᵀ (= ‖d_i Xᵀ‖²),  ey[i] = w_i G w_iᵀ  (reference=True).
+    `out`: a LayerOutput or (alpha, mu, T, perm); perm may be None (identity).  G=None gives ew
+    only.  Stream-ordered, no host synchronisation; bit-defined (DESIGN.md §3 "Layer report")."""
+    alpha, mu, T, perm = (out.alpha, out.mu, out.T, out.perm) if isinstance(out, LayerOutput) else out
+    W = _float_input(W)
+    dev = W.device
+    n, m = W.shape
+    alpha = alpha.to(dev, torch.float32).contiguous()
+    mu = mu.to(dev, torch.float32).contiguous()
+    T = T.to(dev).contiguous()
+    if T.dtype not in (torch.int8, torch.float32):
+        T = T.float()
+    B = num_blocks(m, block_size)
+    if tuple(T.shape) != (n, m) or tuple(alpha.shape) != (n, B) or tuple(mu.shape) != (n, B):
+        raise ValueError(f"layer_report: W {n}x{m}, block {block_size} needs T {n}x{m} and grids {n}x{B}")
+    if perm is not None:
+        perm = perm.to(dev, torch.int64).contiguous()
+    if G is not None:
+        G = G.to(dev)
+        if G.dtype != torch.float32 or tuple(G.shape) != (m, m) or G.stride(1) != 1:
+            raise ValueError("layer_report: G must be an m x m fp32 Gram with unit column stride")
+    flags = _lib.REPORT_REF if (reference and G is not None) else 0
+    L = _lib.lib()
+    ws = _lib.workspace(L.pt2q_layer_report_workspace_bytes(n, m, flags), dev)
+    ew = torch.empty(n, dtype=torch.float32, device=dev)
+    ex = torch.empty_like(ew) if G is not None else None
+    ey = torch.empty_like(ew) if flags else None
+    totals = torch.empty(3, dtype=torch.float32, device=dev)
+    _lib.check(L.pt2q_layer_report(_lib.ptr(W), _lib.dtype_code(W), m, n, m, int(block_size), _lib.ptr(alpha),
+                                   _lib.ptr(mu), _lib.ptr(T), _lib.dtype_code(T), m, _lib.ptr(perm), _lib.ptr(G),
+                                   G.stride(0) if G is not None else 0, flags, _lib.ptr(ew), _lib.ptr(ex),
+                                   _lib.ptr(ey), _lib.ptr(totals), _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+               "pt2q_layer_report")
+    return LayerReport(ew, ex, ey, totals)
+
+
+def quadform_rows(A: torch.Tensor, G: torch.Tensor, total: bool = False):
+    """q[i] = a_i G a_iᵀ for the rows of A (rows x m) and an m x m fp32 G (pt2q_quadform_rows):
+    the product A G stays on chip.  total=True: also the ROWTREE sum of q (device scalar)."""
+    A = _float_input(A)
+    dev = A.device
+    rows, m = A.shape
+    G = G.to(dev)
+    if G.dtype != torch.float32 or tuple(G.shape) != (m, m) or G.stride(1) != 1:
+        raise ValueError("quadform_rows: G must be an m x m fp32 matrix with unit column stride")
+    L = _lib.lib()
+    ws = _lib.workspace(L.pt2q_quadform_rows_workspace_bytes(rows, m), dev)
+    q = torch.empty(rows, dtype=torch.float32, device=dev)
+    tot = torch.empty(1, dtype=torch.float32, device=dev) if total else None
+    _lib.check(L.pt2q_quadform_rows(_lib.ptr(A), _lib.dtype_code(A), m, rows, m, _lib.ptr(G), G.stride(0),
+                                    _lib.ptr(q), _lib.ptr(tot), _lib.ptr(ws), ws.numel(), _lib.stream_of(dev)),
+               "pt2q_quadform_rows")
+    return (q, tot[0]) if total else q
 
 
 def pack_ternary(T: torch.Tensor):

@@ -72,6 +72,17 @@ class GPTQ:
                                  bs).to(self.device, self.dtype)
 
 
+    def error_report(self, reference: bool = True) -> "engine.LayerReport":
+        """The quantization error of the last quantize() from the object's own accumulated Gram
+        (quantizer.py:296-306 in Gram form; engine.layer_report).  self.H is the RAW sum Σ XᵀX of
+        add_batch -- quantize() scales and damps a copy (engine.prepare_hessian), never self.H --
+        so output_error is ‖(W - Ŵ) Xᵀ‖²_F over all nsamples rows, Ŵ = get_quantized_weight()."""
+        if self.last_output is None:
+            raise RuntimeError("Must call quantize() first")
+        return engine.layer_report(self.layer.weight.data.to(self._dev), self.last_output, self.H,
+                                   self.block_size, reference)
+
+
 class GPTQQuantizer:
     """gptq.py:233-272."""
 

@@ -32,6 +32,7 @@ class PT2LLMQuantizer:
         self.device = torch.device(device if device != "cpu" else "cuda")
         self.quantized_params: Dict[str, Dict[str, torch.Tensor]] = {}
         self.last_output = None
+        self.layer_reports: Dict[str, Dict[str, float]] = {}  # quantize(report=True)
         self._ws = None
 
     @torch.no_grad()
@@ -65,7 +66,8 @@ class PT2LLMQuantizer:
 
     @torch.no_grad()
     def quantize(self, calibration_samples=None, writeback: str = "reference",
-                 propagate: str = "model", schedule: str = "grams-first", timings=None):
+                 propagate: str = "model", schedule: str = "grams-first", timings=None,
+                 report: bool = False):
         """main.py:232-308: decoder layer by decoder layer, capture the linears' inputs over the
         calibration forwards, quantise every linear, write the weights back.  The captured
         inputs go straight into per-input Grams (calibration.GramCapture), so q/k/v and gate/up
@@ -82,7 +84,11 @@ class PT2LLMQuantizer:
         inverses batched per width, the block loops grouped by shape on the lanes); "lanes": one
         unit per lane of an engine.UnitPipeline.  Bit-identical.
         timings: a list that receives one dict per decoder layer (wall seconds of capture,
-        quantise, write-back, propagate and the host copies; device-synchronised between them)."""
+        quantise, write-back, propagate and the host copies; device-synchronised between them).
+        report=True: self.layer_reports[name] receives each linear's error report (host floats:
+        weight_error, output_error, reference_energy, relative_output_error, nsamples), computed
+        from its Gram before the write-back (calibration.quantize_decoder_layer); the returned
+        params and the model's weights are those of report=False."""
         import time
         from . import sharding
         if self.model is None:
@@ -127,7 +133,8 @@ class PT2LLMQuantizer:
                 tq[0] = mark()
             res = calibration.quantize_decoder_layer(layer, run_timed, self.block_size, self.use_ssr,
                                                      self.percdamp, idx, writeback, self.device,
-                                                     None if gf is not None else pipe, gf)
+                                                     None if gf is not None else pipe, gf,
+                                                     self.layer_reports if report else None)
             t2 = mark()
             if inputs is not None and idx + 1 < len(layers):
                 inputs = calibration.propagate_layer(layer, inputs)

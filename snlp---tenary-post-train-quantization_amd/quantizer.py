@@ -11,7 +11,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, engine
 
 
 def _dev_f32(t, dev):
@@ -131,3 +131,20 @@ def compute_output_error(W: torch.Tensor, W_c: torch.Tensor, X: torch.Tensor) ->
         X = X.reshape(-1, X.shape[-1])
     diff = (W - W_c) @ X.T
     return (diff ** 2).sum().item()
+
+
+def quadform_rows(A: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
+    """q[i] = a_i G a_iᵀ per row of A (rows x m) for an m x m G, on the current HIP device
+    (engine.quadform_rows); the result comes back on A's device."""
+    dev = _lib.compute_device(A, G)
+    return engine.quadform_rows(A.to(dev), G.to(dev, torch.float32)).to(A.device)
+
+
+def compute_output_error_from_gram(W: torch.Tensor, W_c: torch.Tensor, G: torch.Tensor) -> float:
+    """compute_output_error (quantizer.py:301-306) without the activations: with the raw Gram
+    G = XᵀX (m x m, full symmetric), ‖(W - W_c) Xᵀ‖²_F = Σ_i d_i G d_iᵀ.  D = W - W_c is formed in
+    fp32 torch; the quadratic forms and their sum run in pt2q_quadform_rows."""
+    dev = _lib.compute_device(W, W_c, G)
+    D = W.to(dev, torch.float32) - W_c.to(dev, torch.float32)
+    _, tot = engine.quadform_rows(D, G.to(dev, torch.float32), total=True)
+    return tot.item()
