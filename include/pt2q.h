@@ -377,6 +377,21 @@ int pt2q_ternary_linear(const void* x, int xdtype, int tokens, int64_t ldx, int 
                         const float* mu, int B, int bs, const float* bias, void* y, int ydtype,
                         int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same layer (model.py:75-95) for 1 .. pt2q_ternary_decode_max_tokens() (8) tokens in ONE
+ * launch: no workspace, no allocation, no synchronisation (capturable into a hipGraph).  codes,
+ * gather, alpha, mu, bias, B, bs and the argument rules are those of pt2q_ternary_linear; x needs
+ * only 2-byte alignment and any ldx >= m, y any ldy >= n.  More tokens than the cap, or
+ * m > 32768 (one token's activations, gathered and staged, must fit 128 KiB of LDS), return
+ * PT2Q_E_UNSUPPORTED before anything is launched.  The result is bit-defined (DESIGN.md §3
+ * DOT64P: per-lane fmaf chains over the 16-byte pieces of a packed row, wave butterfly, one
+ * fp32 bias add, one rounding to ydtype) and a token's bits do not depend on the other tokens
+ * of the call; pt2q_ternary_linear's MFMA order differs from it in the last bits. */
+int pt2q_ternary_decode_max_tokens(void);
+int pt2q_ternary_decode(const void* x, int xdtype, int tokens, int64_t ldx, int n, int m,
+                        const uint8_t* codes, const int* gather, const float* alpha,
+                        const float* mu, int B, int bs, const float* bias, void* y, int ydtype,
+                        int64_t ldy, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

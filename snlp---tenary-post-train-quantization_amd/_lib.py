@@ -96,6 +96,8 @@ _SIGS = {
     "pt2q_ternary_pack": (I, [P, I64, I, I, P, I, P, P, P]),
     "pt2q_ternary_linear_workspace_bytes": (SZ, [I, I, I]),
     "pt2q_ternary_linear": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P, SZ, P]),
+    "pt2q_ternary_decode_max_tokens": (I, []),
+    "pt2q_ternary_decode": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_h, _name)
