@@ -392,6 +392,33 @@ int pt2q_ternary_decode(const void* x, int xdtype, int tokens, int64_t ldx, int 
                         const float* mu, int B, int bs, const float* bias, void* y, int ydtype,
                         int64_t ldy, void* stream);
 
+/* count (1 .. PT2Q_DECODE_GROUP_MAX) packed ternary linears that read the same x (tokens x m,
+ * 1 .. 8 tokens), in ONE launch: no workspace, no allocation, no synchronisation, capturable.
+ * The members share m, xdtype and bs; n, codes, gather, alpha, mu, B, bias, y and ldy are HOST
+ * arrays of count entries, read during the call only (the device pointers in them travel in the
+ * kernel's arguments; nothing is copied to the device).  bias may be NULL, and so may any of its
+ * entries.  Per member the argument rules are those of pt2q_ternary_decode.
+ *   PT2Q_DECODE_PLAIN   y[z] (tokens x n[z], ldy[z], ydtype = xdtype or PT2Q_F32) holds what
+ *                       pt2q_ternary_decode writes for member z alone, bit for bit (DOT64P).
+ *   PT2Q_DECODE_SWIGLU  count = 2 (member 0 the gate, member 1 the up projection), n[0] = n[1],
+ *                       ydtype = xdtype: only y[0] / ldy[0] are used, and
+ *                       y[0][t][i] = RN_TY(RN_TY(g * sigmoid(g)) * u) with g, u the two separate
+ *                       calls' outputs -- bit-defined by contract SWIGLU16.  Non-
+ *                       finite g or u give an unspecified value.
+ * PT2Q_E_ARG, nothing launched: count outside 1 .. 4, an unknown epilogue, SWIGLU with
+ * count != 2, n[0] != n[1] or ydtype = PT2Q_F32.  PT2Q_E_UNSUPPORTED, nothing launched: more than
+ * 8 tokens, m > 32768, SWIGLU with m > 20480 (two gathered copies of a token's activations and
+ * its staged row must fit 128 KiB of LDS).  A token's bits do not depend on the other tokens of
+ * the call. */
+#define PT2Q_DECODE_GROUP_MAX 4
+#define PT2Q_DECODE_PLAIN 0
+#define PT2Q_DECODE_SWIGLU 1
+int pt2q_ternary_decode_group(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                              const int* n, const uint8_t* const* codes, const int* const* gather,
+                              const float* const* alpha, const float* const* mu, const int* B, int bs,
+                              const float* const* bias /* array or entries nullable */,
+                              void* const* y, int ydtype, const int64_t* ldy, int epilogue, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,8 @@ Drop-in for the reference's hot-path surface:
     compute_bits_per_weight, evaluate_perplexity                                   (utils.py)
     TernaryLinear, replace_linear_with_ternary                                     (model.py)
     ternary_decode, set_decode               (the fused 1-8 token decode kernel of TernaryLinear)
+    ternary_decode_group, ternary_decode_swiglu, TernaryGatedMLP, fuse_gated_mlp
+                                             (projections sharing x, and gate/up + SwiGLU, in one launch)
 All compute runs in libpt2q.so (HIP, gfx950); importing fails loudly if it is not built.
 """
 from . import _lib
@@ -24,8 +26,9 @@ from .gptq import GPTQ, GPTQQuantizer
 from .pt2llm import PT2LLMQuantizer
 from .calibration import (GramAccumulator, GramCapture, find_linear_layers, get_llm_layers,
                           quantize_decoder_layer)
-from .ternary import (TernaryLinear, compute_bits_per_weight, load_quantized_model,
-                      replace_linear_with_ternary, save_quantized_model, set_decode, ternary_decode)
+from .ternary import (TernaryGatedMLP, TernaryLinear, compute_bits_per_weight, fuse_gated_mlp, load_quantized_model,
+                      replace_linear_with_ternary, save_quantized_model, set_decode, ternary_decode,
+                      ternary_decode_group, ternary_decode_swiglu)
 from .evaluation import evaluate_perplexity
 from .engine import (LayerGraph, LayerOutput, LayerWorkspace, UnitRun, UnitWorkspace, cholesky_inverse,
                      dequantize, error_feedback, fill_synthetic, gram, hessian_inverse, pack_ternary, prepare_hessian,
@@ -45,5 +48,6 @@ __all__ = [
     "UnitPipeline", "sum_partials", "evaluate_perplexity", "compute_cosine_similarity_matrix",
     "get_initial_reorder_indices", "SSRReorderer", "apply_permutation", "apply_permutation_to_input",
     "compute_block_variance", "LayerReport", "layer_report", "quadform_rows", "compute_output_error_from_gram",
-    "ternary_decode", "set_decode",
+    "ternary_decode", "set_decode", "ternary_decode_group", "ternary_decode_swiglu", "TernaryGatedMLP",
+    "fuse_gated_mlp",
 ]

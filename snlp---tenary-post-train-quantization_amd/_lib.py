@@ -22,6 +22,8 @@ FLAG_S1_GIVEN = 0x2
 AGA_NONE, AGA_ACT, AGA_HESS = 0x0, 0x10, 0x20
 AGA_MASK = 0x30
 REPORT_REF = 0x1
+DECODE_GROUP_MAX = 4
+DECODE_PLAIN, DECODE_SWIGLU = 0, 1
 STAGE_INIT, STAGE_GRID, STAGE_ROUND, STAGE_ITF, STAGE_AGA, STAGE_FULL = range(6)
 # stage-timer classes (pt2q_stage_timing, include/pt2q.h PT2Q_TIMER_*)
 TIMERS = ("setup", "ssr", "atq", "ef", "out", "gram", "inverse")
@@ -98,6 +100,7 @@ _SIGS = {
     "pt2q_ternary_linear": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P, SZ, P]),
     "pt2q_ternary_decode_max_tokens": (I, []),
     "pt2q_ternary_decode": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P]),
+    "pt2q_ternary_decode_group": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_h, _name)

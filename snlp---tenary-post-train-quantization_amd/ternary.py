@@ -5,18 +5,23 @@ Buffers and their state_dict names are the reference's (T int8, alpha, mu, perm,
 so checkpoints move between the two.  The forward pass is the libpt2q kernel
 pt2q_ternary_linear (csrc/ternary_linear.hip): 2-bit packed codes dequantised in registers into
 f16/bf16 MFMA operands; decode="fused" sends calls of 1..decode_max_tokens tokens to the
-single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead.  Two semantics:
+single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead; linears that read the
+same x go through pt2q_ternary_decode_group (csrc/ternary_decode_group.hip) in one launch, a gated
+MLP's gate and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP,
+fuse_gated_mlp).  Two semantics:
 
   compat=False (default)  y = x · Ŵᵀ + b with the correct reconstruction of gptq.py:201-230
                           (block k of alpha/mu belongs to columns perm[k·bs:(k+1)·bs]).
   compat=True             exactly what the reference forward computes: contiguous blocks of T
                           and a double permutation (model.py:75-110).
 """
+import ctypes
 import os
 from typing import Dict, Optional
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import _lib
 
@@ -29,6 +34,14 @@ DECODE_MODES = ("mfma", "fused")
 # A caller whose shapes do better may raise it, up to the library's cap.
 DECODE_CROSSOVER_TOKENS = 1
 decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), DECODE_CROSSOVER_TOKENS)
+# Largest token count a TernaryGatedMLP whose children are decode="fused" sends to the SwiGLU
+# kernel and ternary_decode(down_proj); above it the children are called one by one.
+# profiles/ternary_mlp_timing.txt has the fused module below three decode calls plus torch's silu and
+# mul by 7.8-11.2 us at 1 token at every measured shape and dtype; at 2 tokens and above it loses at
+# hidden 5120 (two gathered copies of x leave LDS for one token per workgroup there), so the
+# crossover is 1.  A caller whose shapes do better may raise it, up to the cap.
+MLP_DECODE_CROSSOVER_TOKENS = 1
+mlp_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), MLP_DECODE_CROSSOVER_TOKENS)
 
 
 def _check_mode(decode):
@@ -74,6 +87,104 @@ def ternary_decode(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, a
         _lib.ptr(x), _lib.dtype_code(x), tokens, ldx, n, m, _lib.ptr(codes), _lib.ptr(gather),
         _lib.ptr(alpha), _lib.ptr(mu), B, block_size, _lib.ptr(bias), _lib.ptr(out),
         _lib.dtype_code(out), ldy, _lib.stream_of(x.device)), "pt2q_ternary_decode")
+    return out
+
+
+def _group_members(x, members, block_size, what):
+    """The (codes, gather, alpha, mu, bias) tuples of `members` (TernaryLinear, packed on demand, or
+    such tuples with `block_size`) after the checks of ternary_decode, and their block size."""
+    if not 1 <= len(members) <= _lib.DECODE_GROUP_MAX:
+        raise _lib.Pt2qError(f"{what}: 1..{_lib.DECODE_GROUP_MAX} members, got {len(members)}")
+    _lib.require_device(x)
+    if x.dim() != 2 or x.stride(1) != 1:
+        raise _lib.Pt2qError(f"{what}: x must be tokens x m with unit column stride")
+    m = x.shape[1]
+    P = int(_lib.lib().pt2q_ternary_linear_positions(m))
+    packs = []
+    for mem in members:
+        if isinstance(mem, TernaryLinear):
+            if mem._packed is None:
+                mem._prepare()
+            if block_size is not None and block_size != mem.block_size:
+                raise _lib.Pt2qError(f"{what}: the members share one block size")
+            block_size = mem.block_size
+            if mem.in_features != m or mem.dtype != x.dtype:
+                raise _lib.Pt2qError(f"{what}: the members read x ({m} columns of {x.dtype})")
+            mem = mem._packed
+        codes, gather, alpha, mu, bias = mem
+        for t in (codes, gather, alpha, mu):
+            _lib.require_device(t)
+        if alpha.dtype != torch.float32 or mu.dtype != torch.float32 or alpha.shape != mu.shape or alpha.dim() != 2 or \
+                (bias is not None and bias.dtype != torch.float32):
+            raise _lib.Pt2qError(f"{what}: alpha, mu (n x B) and bias are fp32")
+        if codes.dtype != torch.uint8 or gather.dtype != torch.int32:
+            raise _lib.Pt2qError(f"{what}: codes uint8 and gather int32, as pt2q_ternary_pack writes them")
+        n = alpha.shape[0]
+        if tuple(codes.shape) != (n, P // 4) or gather.numel() != P or (bias is not None and bias.numel() != n):
+            raise _lib.Pt2qError(f"{what}: codes / gather / bias do not match x and alpha")
+        packs.append((codes.contiguous(), gather.contiguous(), alpha.contiguous(), mu.contiguous(),
+                      None if bias is None else bias.contiguous()))
+    if block_size is None:
+        raise _lib.Pt2qError(f"{what}: block_size is needed with packed tuples")
+    return packs, int(block_size)
+
+
+def _decode_group(x, packs, block_size, outs, epilogue, what):
+    tokens, m = x.shape
+    count = len(packs)
+    ns = (ctypes.c_int * count)(*[p[2].shape[0] for p in packs])
+    Bs = (ctypes.c_int * count)(*[p[2].shape[1] for p in packs])
+    ldys = (ctypes.c_int64 * len(outs))(*[o.stride(0) if tokens > 1 else o.shape[1] for o in outs])
+    arrs = [_lib.ptr_array([p[i] for p in packs]) for i in range(5)] + [_lib.ptr_array(outs)]
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    _lib.check(_lib.lib().pt2q_ternary_decode_group(
+        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns),
+        arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0],
+        _lib.dtype_code(outs[0]), as_p(ldys), epilogue, _lib.stream_of(x.device)), what)
+
+
+def _check_out(out, tokens, n, dtype, device, what):
+    if out is None:
+        return torch.empty((tokens, n), dtype=dtype, device=device)
+    if tuple(out.shape) != (tokens, n) or out.dtype != dtype or out.stride(1) != 1 or not out.is_cuda:
+        raise _lib.Pt2qError(f"{what}: out must be tokens x n of the output dtype with unit column stride")
+    return out
+
+
+def ternary_decode_group(x: torch.Tensor, members, out_dtype: Optional[torch.dtype] = None, outs=None,
+                         block_size: Optional[int] = None):
+    """pt2q_ternary_decode_group, PLAIN: 1..4 ternary linears on the same x (1..8 tokens) in one
+    launch -- the q/k/v projections of a host that owns its attention code.  members: TernaryLinear
+    modules (packed on demand) or (codes, gather, alpha, mu, bias) tuples as ternary_decode takes
+    them, then with block_size.  Returns one tokens x n tensor per member (out_dtype: x's dtype or
+    torch.float32; outs: optional tensors to write into), each bit-equal to ternary_decode on that
+    member alone."""
+    what = "ternary_decode_group"
+    packs, bs = _group_members(x, members, block_size, what)
+    tokens = x.shape[0]
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if outs is not None and len(outs) != len(packs):
+        raise _lib.Pt2qError(f"{what}: one out per member")
+    outs = [_check_out(None if outs is None else outs[z], tokens, p[2].shape[0], out_dtype, x.device, what)
+            for z, p in enumerate(packs)]
+    if tokens:
+        _decode_group(x, packs, bs, outs, _lib.DECODE_PLAIN, "pt2q_ternary_decode_group")
+    return outs
+
+
+def ternary_decode_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor] = None,
+                          block_size: Optional[int] = None) -> torch.Tensor:
+    """pt2q_ternary_decode_group, SWIGLU: h = silu(gate(x)) * up(x) for 1..8 tokens in one launch,
+    bit-defined by contract SWIGLU16 from the outputs the two separate
+    ternary_decode calls would give.  gate, up: members as in ternary_decode_group, equal widths;
+    h has x's dtype."""
+    what = "ternary_decode_swiglu"
+    packs, bs = _group_members(x, [gate, up], block_size, what)
+    if packs[0][2].shape[0] != packs[1][2].shape[0]:
+        raise _lib.Pt2qError(f"{what}: gate and up have the same number of rows")
+    out = _check_out(out, x.shape[0], packs[0][2].shape[0], x.dtype, x.device, what)
+    if x.shape[0]:
+        _decode_group(x, packs, bs, [out], _lib.DECODE_SWIGLU, "pt2q_ternary_decode_group")
     return out
 
 
@@ -184,6 +295,76 @@ class TernaryLinear(nn.Module):
         codes, gather, a32, m32, b32 = self._packed
         return (codes.numel() + gather.numel() * 4 + a32.numel() * 4 + m32.numel() * 4 +
                 (b32.numel() * 4 if b32 is not None else 0))
+
+
+class TernaryGatedMLP(nn.Module):
+    """down_proj(silu(gate_proj(x)) * up_proj(x)) over three TernaryLinear children (the names, and
+    so the state_dict keys, of a Llama MLP).  With all three at decode="fused", forwards of
+    1..mlp_decode_max_tokens tokens take two launches -- ternary_decode_swiglu, then
+    ternary_decode on down_proj -- in place of three launches and two elementwise kernels; every
+    other call goes through the children exactly as the unfused MLP does."""
+
+    def __init__(self, gate_proj: TernaryLinear, up_proj: TernaryLinear, down_proj: TernaryLinear):
+        super().__init__()
+        if not _gated_mlp_matches(gate_proj, up_proj, down_proj):
+            raise _lib.Pt2qError("TernaryGatedMLP: gate_proj and up_proj are TernaryLinear of one shape, dtype and "
+                                 "block size, and down_proj reads their width in that dtype")
+        self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        gate, up, down = self.gate_proj, self.up_proj, self.down_proj
+        if gate.decode == up.decode == down.decode == "fused":
+            xt = x.reshape(-1, gate.in_features).to(gate.dtype).contiguous()
+            if 0 < xt.shape[0] <= mlp_decode_max_tokens:
+                if down._packed is None:
+                    down._prepare()
+                h = ternary_decode_swiglu(xt, gate, up)
+                codes, gather, a32, m32, b32 = down._packed
+                y = ternary_decode(h, codes, gather, a32, m32, down.block_size, b32)
+                return y.reshape(*x.shape[:-1], down.out_features)
+        return down(F.silu(gate(x)) * up(x))
+
+
+def _gated_mlp_matches(gate, up, down) -> bool:
+    return all(isinstance(l, TernaryLinear) for l in (gate, up, down)) and \
+        gate.in_features == up.in_features and gate.out_features == up.out_features == down.in_features and \
+        gate.dtype == up.dtype == down.dtype and gate.block_size == up.block_size
+
+
+_SILU_PROBE = (-20.0, -3.0, -1.0, -0.5, 0.0, 0.25, 1.0, 2.5, 8.0, 30.0)
+
+
+def _computes_silu(act_fn) -> bool:
+    """Whether act_fn gives F.silu's values on a fixed small CPU tensor (nn.SiLU, a functional
+    silu, transformers' SiLU class; a GELU does not)."""
+    if not callable(act_fn):
+        return False
+    p = torch.tensor(_SILU_PROBE, dtype=torch.float32)
+    try:
+        with torch.no_grad():
+            r = act_fn(p.clone())
+    except Exception:
+        return False
+    return isinstance(r, torch.Tensor) and r.shape == p.shape and torch.equal(r, F.silu(p))
+
+
+def fuse_gated_mlp(model: nn.Module) -> nn.Module:
+    """Replace every gated MLP of `model` by a TernaryGatedMLP over the same children: a module
+    whose children are TernaryLinear gate_proj, up_proj and down_proj of matching dtypes, widths
+    and block sizes (plus at most its act_fn), with no tensors of its own and an act_fn that
+    computes SiLU.  Everything else -- attention, an MLP with another activation -- is left as it
+    is; state_dict keys do not change."""
+    for parent in list(model.modules()):
+        for name, mod in list(parent.named_children()):
+            kids = dict(mod.named_children())
+            if isinstance(mod, TernaryGatedMLP) or not set(kids) - {"act_fn"} == {"gate_proj", "up_proj", "down_proj"}:
+                continue
+            if list(mod.parameters(recurse=False)) or list(mod.buffers(recurse=False)):
+                continue
+            gate, up, down = kids["gate_proj"], kids["up_proj"], kids["down_proj"]
+            if _gated_mlp_matches(gate, up, down) and _computes_silu(getattr(mod, "act_fn", None)):
+                setattr(parent, name, TernaryGatedMLP(gate, up, down))
+    return model
 
 
 def replace_linear_with_ternary(model: nn.Module, quantized_params: Dict[str, Dict[str, torch.Tensor]],
