@@ -128,7 +128,10 @@ __global__ __launch_bounds__(256) void tl_gemm_kernel(const uint8_t* codes, int 
 #pragma unroll
     for (int g = 0; g < 8; ++g) {
       const int pg = TL_PB * kb + 16 * g;
-      const int blk = pg / bs;
+      // padding positions (pg >= m, code 0, gathered x 0) can have pg / bs = B, one past the row's
+      // scales: clamp as the decode kernels do (ternary_decode.hpp), so no weight is made from
+      // whatever lies there (a NaN times the gathered 0 would be NaN)
+      const int blk = min(pg / bs, B - 1);
       if (blk != tblk) {  // new scale block: rebuild the weight table
         tblk = blk;
         const float a = arow[blk], mm = mrow[blk];
@@ -262,6 +265,8 @@ __global__ __launch_bounds__(256, 2) void tl_prefill_kernel(const uint8_t* codes
                               : (const void*)&tp_zero16;
       __builtin_amdgcn_global_load_lds(src, (lptr)(bsl + (wv * 2 + q) * 1024), 16, 0, 0);
     }
+    // blk <= B - 1 without a clamp: kb * 128 <= P - 128, and for bs % 128 == 0 the multiple of 128
+    // ceil(m / bs) * bs >= m is at least P, so blk < ceil(m / bs) <= B; per-channel has bs = P, blk = 0
     const int f = fb + wv * 64 + lane, blk = (kb * 128) / bs;
     const void* sa = f < n ? (const void*)(alpha + (long)f * B + blk) : (const void*)&tp_zero16;
     const void* sm = f < n ? (const void*)(mu + (long)f * B + blk) : (const void*)&tp_zero16;

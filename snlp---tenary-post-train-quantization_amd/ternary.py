@@ -221,6 +221,17 @@ class TernaryLinear(nn.Module):
     def dtype(self):
         return self.alpha.dtype
 
+    # _packed (codes, fp32 scales, bias) is derived from the buffers: drop it wherever they can
+    # change underneath it -- a state-dict load (on this module or a parent) and every _apply
+    # (.half(), .bfloat16(), .to(), .cuda() on this module or a parent); the next forward repacks.
+    def _load_from_state_dict(self, *args, **kwargs):
+        self._packed = None
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _apply(self, *args, **kwargs):
+        self._packed = None
+        return super()._apply(*args, **kwargs)
+
     def set_quantized_params(self, alpha: torch.Tensor, mu: torch.Tensor, T: torch.Tensor,
                              perm: torch.Tensor, bias: Optional[torch.Tensor] = None):
         """model.py:59-73, then packs the codes for the kernel."""
@@ -427,8 +438,5 @@ def save_quantized_model(model: nn.Module, save_path: str,
 def load_quantized_model(model: nn.Module, load_path: str):
     """utils.py:299-304, with the safe loader (tensors and dicts only)."""
     ckpt = torch.load(load_path, map_location="cpu", weights_only=True)
-    model.load_state_dict(ckpt["model_state_dict"])
-    for mod in model.modules():
-        if isinstance(mod, TernaryLinear):
-            mod._packed = None
+    model.load_state_dict(ckpt["model_state_dict"])  # (every TernaryLinear drops its pack on load)
     return model, ckpt.get("quantized_params", {})

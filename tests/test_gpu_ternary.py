@@ -58,6 +58,8 @@ def test_correct_forward_matches_reconstruction(pt2q, name):
 
 @pytest.mark.parametrize("n,m,bs,tokens,dt", [(4096, 4096, 128, 1, torch.float16),
                                               (4096, 4096, 128, 7, torch.bfloat16),
+                                              # 300 tokens >= 256 with bs = 128: the prefill kernel,
+                                              # ragged m (9 blocks of 128 positions, 52 padded)
                                               (1000, 1100, 128, 300, torch.float16),
                                               (640, 520, 520, 33, torch.bfloat16),
                                               (4096, 11008, 128, 64, torch.float16),
