@@ -129,7 +129,7 @@ __global__ __launch_bounds__(256) void tl_gemm_kernel(const uint8_t* codes, int 
     for (int g = 0; g < 8; ++g) {
       const int pg = TL_PB * kb + 16 * g;
       // padding positions (pg >= m, code 0, gathered x 0) can have pg / bs = B, one past the row's
-      // scales: clamp as the decode kernels do (ternary_decode.hpp), so no weight is made from
+      // scales: clamp as the decode kernel does (ternary_decode.hip), so no weight is made from
       // whatever lies there (a NaN times the gathered 0 would be NaN)
       const int blk = min(pg / bs, B - 1);
       if (blk != tblk) {  // new scale block: rebuild the weight table

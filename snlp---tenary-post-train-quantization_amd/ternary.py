@@ -6,9 +6,9 @@ so checkpoints move between the two.  The forward pass is the libpt2q kernel
 pt2q_ternary_linear (csrc/ternary_linear.hip): 2-bit packed codes dequantised in registers into
 f16/bf16 MFMA operands; decode="fused" sends calls of 1..decode_max_tokens tokens to the
 single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead; linears that read the
-same x go through pt2q_ternary_decode_group (csrc/ternary_decode_group.hip) in one launch, a gated
-MLP's gate and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP,
-fuse_gated_mlp).  Two semantics:
+same x go through pt2q_ternary_decode_group (the same kernel) in one launch, a gated MLP's gate
+and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp).
+Two semantics:
 
   compat=False (default)  y = x · Ŵᵀ + b with the correct reconstruction of gptq.py:201-230
                           (block k of alpha/mu belongs to columns perm[k·bs:(k+1)·bs]).
@@ -58,41 +58,26 @@ def ternary_decode(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, a
     (n x P/4 uint8) and gather (P int32) from pt2q_ternary_pack; alpha, mu: n x B fp32; bias: n fp32
     or None; out_dtype: x's dtype (default) or torch.float32; out: an optional tokens x n tensor of
     that dtype with unit column stride to write into."""
-    for t in (x, codes, gather, alpha, mu):
-        _lib.require_device(t)
-    if x.dim() != 2 or x.stride(1) != 1:
-        raise _lib.Pt2qError("ternary_decode: x must be tokens x m with unit column stride")
-    if alpha.dtype != torch.float32 or mu.dtype != torch.float32 or alpha.shape != mu.shape or \
-            (bias is not None and bias.dtype != torch.float32):
-        raise _lib.Pt2qError("ternary_decode: alpha, mu (n x B) and bias are fp32")
-    if codes.dtype != torch.uint8 or gather.dtype != torch.int32:
-        raise _lib.Pt2qError("ternary_decode: codes uint8 and gather int32, as pt2q_ternary_pack writes them")
+    what = "ternary_decode"
+    packs, bs = _group_members(x, [(codes, gather, alpha, mu, bias)], block_size, what)
+    codes, gather, alpha, mu, bias = packs[0]
     tokens, m = x.shape
     n, B = alpha.shape
-    P = int(_lib.lib().pt2q_ternary_linear_positions(m))
-    if tuple(codes.shape) != (n, P // 4) or gather.numel() != P or (bias is not None and bias.numel() != n):
-        raise _lib.Pt2qError("ternary_decode: codes / gather / bias do not match x and alpha")
-    out_dtype = x.dtype if out_dtype is None else out_dtype
-    if out is None:
-        out = torch.empty((tokens, n), dtype=out_dtype, device=x.device)
-    elif tuple(out.shape) != (tokens, n) or out.dtype != out_dtype or out.stride(1) != 1 or not out.is_cuda:
-        raise _lib.Pt2qError("ternary_decode: out must be tokens x n of out_dtype with unit column stride")
+    out = _check_out(out, tokens, n, x.dtype if out_dtype is None else out_dtype, x.device, what)
     if tokens == 0:
         return out
-    codes, gather, alpha, mu = codes.contiguous(), gather.contiguous(), alpha.contiguous(), mu.contiguous()
-    bias = None if bias is None else bias.contiguous()
     ldx = x.stride(0) if tokens > 1 else m
     ldy = out.stride(0) if tokens > 1 else n
     _lib.check(_lib.lib().pt2q_ternary_decode(
         _lib.ptr(x), _lib.dtype_code(x), tokens, ldx, n, m, _lib.ptr(codes), _lib.ptr(gather),
-        _lib.ptr(alpha), _lib.ptr(mu), B, block_size, _lib.ptr(bias), _lib.ptr(out),
+        _lib.ptr(alpha), _lib.ptr(mu), B, bs, _lib.ptr(bias), _lib.ptr(out),
         _lib.dtype_code(out), ldy, _lib.stream_of(x.device)), "pt2q_ternary_decode")
     return out
 
 
 def _group_members(x, members, block_size, what):
     """The (codes, gather, alpha, mu, bias) tuples of `members` (TernaryLinear, packed on demand, or
-    such tuples with `block_size`) after the checks of ternary_decode, and their block size."""
+    such tuples with `block_size`) after the checks every decode call makes, and their block size."""
     if not 1 <= len(members) <= _lib.DECODE_GROUP_MAX:
         raise _lib.Pt2qError(f"{what}: 1..{_lib.DECODE_GROUP_MAX} members, got {len(members)}")
     _lib.require_device(x)

@@ -1,5 +1,5 @@
-"""CPU restatement of contract SWIGLU16, the epilogue of the grouped decode kernel
-(csrc/ternary_decode_group.hip), in numpy float32 -- a plain helper for the group tests, not a
+"""CPU restatement of contract SWIGLU16, the SWIGLU epilogue of the decode kernel
+(csrc/ternary_decode.hip), in numpy float32 -- a plain helper for the group tests, not a
 conftest.  g and u come from DOT64P (tests/ternary_decode_ref.py: fold, finish, round16).
 
   g = RN_TY(v_gate + bias_gate),  u = RN_TY(v_up + bias_up)

@@ -53,6 +53,52 @@ def test_bit_exact_vs_restatement(pt2q, n, m, bs, tokens, dtype, bias, f32out):
     assert np.array_equal(host(y.float()), want)
 
 
+# n = 5 rows, 3 tokens: a single workgroup whose waves 5-7 own no row, and a token count that is no
+# multiple of the 4 tokens a workgroup takes -- unless ref.SHAPES already has such a case
+FEW_ROWS = [] if any(s[0] < 8 for s in ref.SHAPES) else [(5, 100, 16, 3, "bf16")]
+
+
+@pytest.mark.parametrize("n,m,bs,tokens,dtype", FEW_ROWS)
+def test_fewer_rows_than_waves(pt2q, n, m, bs, tokens, dtype):
+    c, d = device_case(pt2q, n, m, bs, tokens, dtype)
+    assert np.array_equal(host(run(pt2q, d, bs).float()), ref.reference(c))
+
+
+def test_single_entry_argument_errors_launch_nothing(pt2q):
+    """The C entry pt2q_ternary_decode itself, by status: a valid call, then every refusal, after
+    which y still holds its sentinel."""
+    L = pt2q._lib
+    E_ARG, E_UNSUPPORTED = 1, 3
+    n, m, bs, tokens, dtype = ref.SHAPES[0]
+    assert (n, m, bs, tokens, dtype) == (33, 100, 16, 2, "fp16")
+    c, d = device_case(pt2q, n, m, bs, tokens, dtype)
+    x = d["x"]
+    B = d["alpha"].shape[1]
+
+    def call(ntok=tokens, mm=m, Bv=B, bsv=bs, ldx=None, ldy=n, ydtype=torch.float16, null=None):
+        y = torch.full((tokens, n), -77.0, dtype=torch.float16, device=x.device)
+        p = {k: None if k == null else L.ptr(t) for k, t in (("codes", d["codes"]), ("gather", d["gather"]), ("y", y))}
+        rc = L.lib().pt2q_ternary_decode(L.ptr(x), L.dtype_code(x), ntok, mm if ldx is None else ldx, n, mm,
+                                         p["codes"], p["gather"], L.ptr(d["alpha"]), L.ptr(d["mu"]), Bv, bsv,
+                                         L.ptr(d["bias"]), p["y"], L._DT[ydtype], ldy, L.stream_of(x.device))
+        torch.cuda.synchronize()
+        if rc == 0:
+            assert np.array_equal(host(y.float()), ref.reference(c))
+        else:
+            assert bool((y == -77.0).all())
+        return rc
+
+    assert call() == 0  # the harness itself is a valid call
+    assert call(null="codes") == E_ARG and call(null="gather") == E_ARG and call(null="y") == E_ARG
+    assert call(ldx=m - 1) == E_ARG and call(ldy=n - 1) == E_ARG
+    assert call(Bv=B - 1) == E_ARG
+    assert call(ntok=0) == E_ARG
+    assert call(ydtype=torch.bfloat16) == E_ARG
+    assert call(ntok=9) == E_UNSUPPORTED
+    assert call(bsv=24) == E_UNSUPPORTED  # below m, not a multiple of 16
+    assert call(mm=32769, Bv=-(-32769 // bs)) == E_UNSUPPORTED
+
+
 @pytest.mark.parametrize("n,m,bs,tokens,dtype", ref.SHAPES[:3])
 def test_pack_matches_restated_layout(pt2q, n, m, bs, tokens, dtype):
     """The buffers the kernel consumes are the ones the restatement builds its positions from."""

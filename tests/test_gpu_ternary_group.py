@@ -1,4 +1,4 @@
-"""The grouped decode entry (pt2q_ternary_decode_group, csrc/ternary_decode_group.hip): a PLAIN
+"""The grouped decode entry (pt2q_ternary_decode_group, csrc/ternary_decode.hip): a PLAIN
 group against pt2q_ternary_decode on each member alone and the DOT64P restatement, the SWIGLU
 epilogue against the numpy restatement of contract SWIGLU16 (tests/ternary_group_ref.py), bit for
 bit; TernaryGatedMLP and fuse_gated_mlp on top of them."""
