@@ -419,6 +419,39 @@ int pt2q_ternary_decode_group(const void* x, int xdtype, int tokens, int64_t ldx
                               const float* const* bias /* array or entries nullable */,
                               void* const* y, int ydtype, const int64_t* ldy, int epilogue, void* stream);
 
+/* y[t] = RMSNorm(x[t]) by contract RMSNORM16: the Llama form
+ * weight * (x.float() * rsqrt(mean(x²) + eps)).to(xdtype), bit-defined -- 512 fmaf chains over the
+ * elements i ≡ j (mod 512), a butterfly per 64 of them, the eight sums added in order, a correctly
+ * rounded division, square root and reciprocal, then two roundings to xdtype.  x, y: tokens x m of
+ * xdtype (fp16 or bf16; anything else PT2Q_E_UNSUPPORTED), unit column stride, ldx, ldy >= m;
+ * weight: m elements of xdtype; any tokens >= 1 (one workgroup per token); y may be x.  A NULL
+ * pointer, ldx or ldy < m, or an eps that is negative, infinite or NaN is PT2Q_E_ARG, nothing
+ * launched.  The Gemma form (1 + weight) is not covered.  No workspace, capturable. */
+int pt2q_rmsnorm(const void* x, int xdtype, int tokens, int64_t ldx, int m, const void* weight, float eps,
+                 void* y, int64_t ldy, void* stream);
+
+/* pt2q_ternary_decode_group with an RMSNorm prologue and a residual epilogue, still ONE launch.
+ *   norm_weight  NULL, or m elements of xdtype: the members read RMSNORM16(x, norm_weight, norm_eps)
+ *                in place of x, with the bits pt2q_rmsnorm would have written (every workgroup
+ *                normalises the rows it stages; x itself is not written).  PLAIN and SWIGLU.
+ *   residual     NULL, or a host array with one entry per output, each NULL or tokens x n[z] of
+ *                ydtype with leading dimension ldr[z] >= n[z]: y[z] = RN_TY(f32(RN_TY(v + bias)) +
+ *                f32(residual[z])), contract RESADD16 -- the bits of residual + (the call without
+ *                it) as an elementwise 16-bit add gives them.  residual[z] may be y[z] itself.
+ *                PLAIN only, ydtype = xdtype.
+ * All rules of pt2q_ternary_decode_group hold.  PT2Q_E_ARG, nothing launched: norm_weight with an
+ * eps that is negative, infinite or NaN; a residual entry with ydtype = PT2Q_F32, with SWIGLU,
+ * with ldr NULL or ldr[z] < n[z].  With norm_weight NULL and no residual entry the call is
+ * pt2q_ternary_decode_group; a group of one has the bits of pt2q_ternary_decode. */
+int pt2q_ternary_decode_fused(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                              const int* n, const uint8_t* const* codes, const int* const* gather,
+                              const float* const* alpha, const float* const* mu, const int* B, int bs,
+                              const float* const* bias /* array or entries nullable */,
+                              void* const* y, int ydtype, const int64_t* ldy, int epilogue,
+                              const void* norm_weight, float norm_eps,
+                              const void* const* residual /* array or entries nullable */,
+                              const int64_t* ldr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,8 @@ Drop-in for the reference's hot-path surface:
     ternary_decode, set_decode               (the fused 1-8 token decode kernel of TernaryLinear)
     ternary_decode_group, ternary_decode_swiglu, TernaryGatedMLP, fuse_gated_mlp
                                              (projections sharing x, and gate/up + SwiGLU, in one launch)
+    rms_norm, TernaryMLPBlock                (RMSNorm as a kernel and as the decode kernel's prologue,
+                                              the residual add as its epilogue: h + mlp(norm(h)) in two launches)
 All compute runs in libpt2q.so (HIP, gfx950); importing fails loudly if it is not built.
 """
 from . import _lib
@@ -26,9 +28,9 @@ from .gptq import GPTQ, GPTQQuantizer
 from .pt2llm import PT2LLMQuantizer
 from .calibration import (GramAccumulator, GramCapture, find_linear_layers, get_llm_layers,
                           quantize_decoder_layer)
-from .ternary import (TernaryGatedMLP, TernaryLinear, compute_bits_per_weight, fuse_gated_mlp, load_quantized_model,
-                      replace_linear_with_ternary, save_quantized_model, set_decode, ternary_decode,
-                      ternary_decode_group, ternary_decode_swiglu)
+from .ternary import (TernaryGatedMLP, TernaryLinear, TernaryMLPBlock, compute_bits_per_weight, fuse_gated_mlp,
+                      load_quantized_model, replace_linear_with_ternary, rms_norm, save_quantized_model, set_decode,
+                      ternary_decode, ternary_decode_group, ternary_decode_swiglu)
 from .evaluation import evaluate_perplexity
 from .engine import (LayerGraph, LayerOutput, LayerWorkspace, UnitRun, UnitWorkspace, cholesky_inverse,
                      dequantize, error_feedback, fill_synthetic, gram, hessian_inverse, pack_ternary, prepare_hessian,
@@ -49,5 +51,5 @@ __all__ = [
     "get_initial_reorder_indices", "SSRReorderer", "apply_permutation", "apply_permutation_to_input",
     "compute_block_variance", "LayerReport", "layer_report", "quadform_rows", "compute_output_error_from_gram",
     "ternary_decode", "set_decode", "ternary_decode_group", "ternary_decode_swiglu", "TernaryGatedMLP",
-    "fuse_gated_mlp",
+    "fuse_gated_mlp", "rms_norm", "TernaryMLPBlock",
 ]

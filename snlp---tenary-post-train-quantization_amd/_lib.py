@@ -101,6 +101,8 @@ _SIGS = {
     "pt2q_ternary_decode_max_tokens": (I, []),
     "pt2q_ternary_decode": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P]),
     "pt2q_ternary_decode_group": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P]),
+    "pt2q_rmsnorm": (I, [P, I, I, I64, I, P, F, P, I64, P]),
+    "pt2q_ternary_decode_fused": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, F, P, P, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_h, _name)

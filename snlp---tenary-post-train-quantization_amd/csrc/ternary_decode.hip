@@ -34,6 +34,17 @@
 //           the items (row, round, member) with the member innermost: ring slot s holds member
 //           s % 2, so the member of an item is known at compile time and both chains keep the
 //           four loads in flight of the plain kernel.
+//
+// pt2q_ternary_decode_fused adds two switches to the same body (template parameter TdFx, arguments
+// TdExtra; the plain entries' kernels carry neither and compile to what they were):
+//   norm      contract RMSNORM16 on the staged rows, in place, before the gather: the
+//             squares are accumulated while staging, the wave sums pass through the head of the
+//             gathered image (no LDS of its own), one more barrier.  All three uses.
+//   residual  contract RESADD16 at the store: y = RN_TY(f32(RN_TY(v + bias)) + f32(res)), per
+//             output, res possibly y.  Single and PLAIN.
+// pt2q_rmsnorm is RMSNORM16 as a kernel of its own, one workgroup per token.
+#include <cfloat>
+
 #include "common.hpp"
 #include "internal.hpp"
 
@@ -239,9 +250,43 @@ PT2Q_DEV float td_sigmoid(float g) {
   return (g >= 0.0f ? 1.0f : e) / (1.0f + e);
 }
 
+// What pt2q_ternary_decode_fused adds to a call, as a by-value argument of the kernels that take it
+// (tl_decode_fused_kernel, tl_decode_one_fused_kernel).  The kernels of the plain entries do not
+// carry it: their argument blocks and their code are what they were.
+struct TdExtra {
+  const uint16_t* nw;  // RMSNORM16 weight, m elements of x's dtype (TD_FX_NORM)
+  float eps;
+  const void* res[PT2Q_DECODE_GROUP_MAX];  // RESADD16: per output, NULL for none
+  long ldr[PT2Q_DECODE_GROUP_MAX];
+};
+// TD_FX_NONE: the plain entries.  TD_FX_RES: residual epilogue.  TD_FX_NORM: norm prologue, and the
+// residual epilogue where the use has one (not SWIGLU).
+enum TdFx { TD_FX_NONE, TD_FX_RES, TD_FX_NORM };
+
+// r of contract RMSNORM16 from the eight wave sums of a row's squares: the sums
+// added in order, then a division, an add, a square root and a division, each the correctly
+// rounded fp32 operation (hipcc's default for / and sqrtf; no fast-math, no contraction).
+PT2Q_DEV float td_norm_r(const float* sums, int m, float eps) {
+  float ss = sums[0];
+#pragma unroll
+  for (int k = 1; k < TD_WAVES; ++k) ss = ss + sums[k];
+  const float mean = ss / (float)m;
+  return 1.0f / sqrtf(mean + eps);
+}
+// RN_TX(RN_TX(xf * r) * wf): both products fp32 values of their own (td_rounded)
+template <bool BF16>
+PT2Q_DEV uint16_t td_normed(uint32_t xu, uint32_t wu, float r) {
+  const float xn = td_round<BF16>(td_rounded(td_lo<BF16>(xu) * r));
+  return (uint16_t)td_bits<BF16>(td_rounded(xn * td_lo<BF16>(wu)));
+}
+constexpr int TD_NORM_PREFETCH = 16;  // weight elements a thread loads ahead of the sums' barrier: m <= 8192
+
 // The kernel's body: all of a workgroup's work for the group G.
-template <bool BF16, int TG, bool SWIGLU>
-PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, int bse, int yf32, const TdGroup& G) {
+template <bool BF16, int TG, bool SWIGLU, TdFx FX>
+PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, int bse, int yf32, const TdGroup& G,
+                        const TdExtra& X) {
+  constexpr bool NORM = FX == TD_FX_NORM;
+  constexpr bool RES = FX != TD_FX_NONE && !SWIGLU;
   constexpr int NZ = SWIGLU ? 2 : 1;  // members a wave computes per row
   static_assert(TD_DEPTH % NZ == 0, "ring slot s holds member s % NZ");
   extern __shared__ __attribute__((aligned(16))) uint8_t td_smem[];
@@ -347,14 +392,67 @@ PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, i
     for (int j = 0; j < 8; ++j) gn[zz][j] = -1;
     load_gi(M[zz].gather, threadIdx.x, gn[zz]);
   }
+  // NORM (RMSNORM16): thread j's chain of squares over the elements it stages is partial j; the
+  // eight wave sums per token go to the head of the gathered image, which nothing has written yet,
+  // and after the barrier every thread normalises the elements it staged, in place.  The weight
+  // is loaded coalesced, its first TD_NORM_PREFETCH elements per thread ahead of that barrier.
+  uint32_t wpre[NORM ? TD_NORM_PREFETCH : 1];
+  if constexpr (NORM) {
+#pragma unroll
+    for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+      const int i = threadIdx.x + j * TD_THREADS;
+      wpre[j] = i < m ? X.nw[i] : 0u;
+    }
+  }
+  float ssq[TG];
 #pragma unroll
   for (int t = 0; t < TG; ++t) {
+    ssq[t] = 0.0f;
     if (t0 + t < tokens) {
       const uint16_t* xr = x + (long)(t0 + t) * ldx;
-      for (int i = threadIdx.x; i < m; i += TD_THREADS) raw[t * rawstride + i] = xr[i];
+      for (int i = threadIdx.x; i < m; i += TD_THREADS) {
+        const uint16_t u = xr[i];
+        raw[t * rawstride + i] = u;
+        if constexpr (NORM) {
+          const float xf = td_lo<BF16>(u);
+          ssq[t] = fmaf(xf, xf, ssq[t]);
+        }
+      }
+    }
+  }
+  if constexpr (NORM) {
+    float* sums = (float*)td_smem;  // [token][wave]
+#pragma unroll
+    for (int t = 0; t < TG; ++t) {
+      const float s = bfly64(ssq[t]);
+      if (lane == 0) sums[t * TD_WAVES + wv] = s;
     }
   }
   __syncthreads();
+  if constexpr (NORM) {
+    const float* sums = (const float*)td_smem;
+    float r[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) r[t] = td_norm_r(sums + t * TD_WAVES, m, X.eps);
+#pragma unroll
+    for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+      const int i = threadIdx.x + j * TD_THREADS;
+      if (i < m) {
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+          if (t0 + t < tokens) raw[t * rawstride + i] = td_normed<BF16>(raw[t * rawstride + i], wpre[j], r[t]);
+        }
+      }
+    }
+    for (int i = threadIdx.x + TD_NORM_PREFETCH * TD_THREADS; i < m; i += TD_THREADS) {
+      const uint32_t wu = X.nw[i];
+#pragma unroll
+      for (int t = 0; t < TG; ++t) {
+        if (t0 + t < tokens) raw[t * rawstride + i] = td_normed<BF16>(raw[t * rawstride + i], wu, r[t]);
+      }
+    }
+    __syncthreads();  // the sums are read, the rows normalised: the gather may overwrite the one and read the other
+  }
 #pragma unroll
   for (int zz = 0; zz < NZ; ++zz) {
     u32x4* xs = xs_of(zz);
@@ -402,13 +500,27 @@ PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, i
     fetch(zc, frow, fk, slot);
     step(zc, frow, fk);
     if (k == 0) bv[Z] = it.bv;
+    const bool last = Z == NZ - 1 && k == nround - 1;  // the row's last item: fold and store
+    // RESADD16: the residual of the elements this lane will store, asked for ahead of the piece
+    const uint16_t* res = nullptr;
+    float resv[TG];
+#pragma unroll
+    for (int t = 0; t < TG; ++t) resv[t] = 0.0f;
+    if constexpr (RES) {
+      res = (const uint16_t*)td_pick(X.res, z);
+      if (last && res && lane == 0) {
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+          if (t0 + t < tokens) resv[t] = td_lo<BF16>(res[(long)(t0 + t) * td_pick(X.ldr, z) + row]);
+        }
+      }
+    }
     const int q = 64 * k + lane;
     if (q < npieces) {
       td_piece<BF16, TG>(xs_of(Z) + (long)k * TG * 512 + lane, it, perpiece, q, bse, M[Z].B,
                          M[Z].alpha + (long)row * M[Z].B, M[Z].mu + (long)row * M[Z].B, acc[Z]);
     }
     const int r0 = row;
-    const bool last = Z == NZ - 1 && k == nround - 1;  // the row's last item: fold and store
     step(zc, row, k);
     if (last) {
 #pragma unroll
@@ -426,9 +538,12 @@ PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, i
               ((_Float16*)G.y[0])[o] = (_Float16)h;
           }
         } else {
-          const float v = biased(0, t);
+          float v = biased(0, t);
           void* y = td_pick(G.y, z);
           if (st) {
+            if constexpr (RES) {  // the lane that stores an element is the one that read it: res may be y
+              if (res) v = td_rounded(td_round<BF16>(v) + resv[t]);
+            }
             if (yf32)
               ((float*)y)[o] = v;
             else if constexpr (BF16)
@@ -450,7 +565,14 @@ PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, i
 template <bool BF16, int TG, bool SWIGLU>
 __global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_kernel(const uint16_t* x, long ldx, int tokens, int m, int P,
                                                                   int bse, int yf32, TdGroup G) {
-  td_decode<BF16, TG, SWIGLU>(x, ldx, tokens, m, P, bse, yf32, G);
+  td_decode<BF16, TG, SWIGLU, TD_FX_NONE>(x, ldx, tokens, m, P, bse, yf32, G, TdExtra{});
+}
+
+// The group with the norm prologue and / or the residual epilogue (pt2q_ternary_decode_fused).
+template <bool BF16, int TG, bool SWIGLU, TdFx FX>
+__global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_fused_kernel(const uint16_t* x, long ldx, int tokens, int m,
+                                                                        int P, int bse, int yf32, TdGroup G, TdExtra X) {
+  td_decode<BF16, TG, SWIGLU, FX>(x, ldx, tokens, m, P, bse, yf32, G, X);
 }
 
 // The same body for a PLAIN group of one whose member arrives as plain arguments.  Through
@@ -459,18 +581,74 @@ __global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_kernel(const uint16_t
 // 1-token call of 6-15 us measured 0.6-0.8 us slower (profiles/ternary_decode_unify_ab.txt; the
 // chain is read off the assembly, not timed apart).  Here every entry of the group is the one
 // member, so the picks fold away and the pointers come with the first kernarg load.
-template <bool BF16, int TG>
-__global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_one_kernel(const uint16_t* x, long ldx, int tokens, int m,
-                                                                      int P, int bse, int yf32, TdMember M, void* y,
-                                                                      long ldy) {
+template <bool BF16, int TG, TdFx FX>
+PT2Q_DEV void td_decode_one(const uint16_t* x, long ldx, int tokens, int m, int P, int bse, int yf32, const TdMember& M,
+                            void* y, long ldy, const uint16_t* nw, float eps, const void* res, long ldr) {
   TdGroup G;
+  TdExtra X;
+  X.nw = nw, X.eps = eps;
 #pragma unroll
   for (int z = 0; z < PT2Q_DECODE_GROUP_MAX; ++z) {
     G.codes[z] = M.codes, G.gather[z] = M.gather, G.alpha[z] = M.alpha, G.mu[z] = M.mu, G.bias[z] = M.bias;
     G.y[z] = y, G.ldy[z] = ldy, G.n[z] = M.n, G.B[z] = M.B;
     G.wg_end[z] = gridDim.x;
+    X.res[z] = res, X.ldr[z] = ldr;
   }
-  td_decode<BF16, TG, false>(x, ldx, tokens, m, P, bse, yf32, G);
+  td_decode<BF16, TG, false, FX>(x, ldx, tokens, m, P, bse, yf32, G, X);
+}
+template <bool BF16, int TG>
+__global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_one_kernel(const uint16_t* x, long ldx, int tokens, int m,
+                                                                      int P, int bse, int yf32, TdMember M, void* y,
+                                                                      long ldy) {
+  td_decode_one<BF16, TG, TD_FX_NONE>(x, ldx, tokens, m, P, bse, yf32, M, y, ldy, nullptr, 0.0f, nullptr, 0);
+}
+// the single linear of pt2q_ternary_decode_fused: the extras as plain arguments too
+template <bool BF16, int TG, TdFx FX>
+__global__ __launch_bounds__(TD_THREADS, 4) void tl_decode_one_fused_kernel(const uint16_t* x, long ldx, int tokens,
+                                                                            int m, int P, int bse, int yf32, TdMember M,
+                                                                            void* y, long ldy, const uint16_t* nw,
+                                                                            float eps, const void* res, long ldr) {
+  td_decode_one<BF16, TG, FX>(x, ldx, tokens, m, P, bse, yf32, M, y, ldy, nw, eps, res, ldr);
+}
+
+// RMSNORM16 from x to y, one workgroup per token: thread j's chain is partial j, so the order is the
+// prologue's by construction.  A thread keeps its first TD_NORM_PREFETCH elements in registers and
+// reads the others again; it writes only elements it read itself, so y may be x.
+template <bool BF16>
+__global__ __launch_bounds__(TD_THREADS) void tl_rmsnorm_kernel(const uint16_t* x, long ldx, int m, const uint16_t* w,
+                                                                float eps, uint16_t* y, long ldy) {
+  __shared__ float sums[TD_WAVES];
+  const uint16_t* xr = x + (long)blockIdx.x * ldx;
+  uint16_t* yr = y + (long)blockIdx.x * ldy;
+  uint32_t xc[TD_NORM_PREFETCH], wc[TD_NORM_PREFETCH];
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    const int i = threadIdx.x + j * TD_THREADS;
+    xc[j] = i < m ? xr[i] : 0u;
+    wc[j] = i < m ? w[i] : 0u;
+  }
+  float acc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    if ((int)threadIdx.x + j * TD_THREADS < m) {
+      const float xf = td_lo<BF16>(xc[j]);
+      acc = fmaf(xf, xf, acc);
+    }
+  }
+  for (int i = threadIdx.x + TD_NORM_PREFETCH * TD_THREADS; i < m; i += TD_THREADS) {
+    const float xf = td_lo<BF16>(xr[i]);
+    acc = fmaf(xf, xf, acc);
+  }
+  acc = bfly64(acc);
+  if ((threadIdx.x & 63) == 0) sums[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  const float r = td_norm_r(sums, m, eps);
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    const int i = threadIdx.x + j * TD_THREADS;
+    if (i < m) yr[i] = td_normed<BF16>(xc[j], wc[j], r);
+  }
+  for (int i = threadIdx.x + TD_NORM_PREFETCH * TD_THREADS; i < m; i += TD_THREADS) yr[i] = td_normed<BF16>(xr[i], w[i], r);
 }
 
 int td_cus() {
@@ -488,14 +666,18 @@ struct TdPlan {  // what a valid call launches
   size_t lds;
   bool bf16, swiglu, yf32;
   TdGroup G;  // the members and, PLAIN, the wg_end table
+  TdFx fx;    // what the call asks beyond the plain entries, and the arguments of that
+  TdExtra X;
 };
 
-// The argument rules of both entries (include/pt2q.h) and, for a call that passes them, its plan.
-// The member arrays hold `count` entries (y, ldy: one per output the call writes).
+// The argument rules of all three entries (include/pt2q.h) and, for a call that passes them, its
+// plan.  The member arrays hold `count` entries (y, ldy, residual, ldr: one per output the call
+// writes).  norm_weight and residual are NULL from the plain entries.
 int td_plan(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count, const int* n,
             const uint8_t* const* codes, const int* const* gather, const float* const* alpha, const float* const* mu,
             const int* B, int bs, const float* const* bias, void* const* y, int ydtype, const int64_t* ldy,
-            int epilogue, TdPlan& p) {
+            int epilogue, const void* norm_weight, float norm_eps, const void* const* residual, const int64_t* ldr,
+            TdPlan& p) {
   if (!x || !n || !codes || !gather || !alpha || !mu || !B || !y || !ldy || tokens <= 0 || m <= 0 || ldx < m ||
       bs <= 0 || count < 1 || count > PT2Q_DECODE_GROUP_MAX)
     return PT2Q_E_ARG;
@@ -506,6 +688,13 @@ int td_plan(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count
   for (int z = 0; z < count; ++z) {
     if (!codes[z] || !gather[z] || !alpha[z] || !mu[z] || n[z] <= 0 || B[z] <= 0) return PT2Q_E_ARG;
     if (z < nout && (!y[z] || ldy[z] < n[z])) return PT2Q_E_ARG;
+  }
+  if (norm_weight && !(norm_eps >= 0.0f && norm_eps <= FLT_MAX)) return PT2Q_E_ARG;  // finite, not NaN
+  bool anyres = false;
+  for (int z = 0; residual && z < nout; ++z) {
+    if (!residual[z]) continue;
+    if (swiglu || ydtype == PT2Q_F32 || !ldr || ldr[z] < n[z]) return PT2Q_E_ARG;  // RESADD16 is 16-bit, and h has no residual
+    anyres = true;
   }
   if (xdtype != PT2Q_F16 && xdtype != PT2Q_BF16) return PT2Q_E_UNSUPPORTED;
   if (ydtype != xdtype && ydtype != PT2Q_F32) return PT2Q_E_ARG;
@@ -553,7 +742,11 @@ int td_plan(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count
     p.G.n[z] = n[s], p.G.B[z] = B[s];
     p.G.y[z] = s < nout ? y[s] : nullptr, p.G.ldy[z] = s < nout ? (long)ldy[s] : 0;
     if (z >= count) p.G.wg_end[z] = p.wgs;
+    const bool r = anyres && s < nout && residual[s];
+    p.X.res[z] = r ? residual[s] : nullptr, p.X.ldr[z] = r ? (long)ldr[s] : 0;
   }
+  p.X.nw = (const uint16_t*)norm_weight, p.X.eps = norm_weight ? norm_eps : 0.0f;
+  p.fx = norm_weight ? TD_FX_NORM : anyres ? TD_FX_RES : TD_FX_NONE;
   p.bf16 = xdtype == PT2Q_BF16, p.swiglu = swiglu, p.yf32 = ydtype == PT2Q_F32;
   return PT2Q_OK;
 }
@@ -576,31 +769,35 @@ bool td_launch_kernel(const TdPlan& p, const void* x, int tokens, int64_t ldx, i
   return true;
 }
 
-template <bool BF16, int TG, TdUse USE>
+template <bool BF16, int TG, TdUse USE, TdFx FX>
 bool td_launch_as(const TdPlan& p, const void* x, int tokens, int64_t ldx, int m, hipStream_t st) {
   const TdGroup& G = p.G;
-  if constexpr (USE == TD_ONE)
-    return td_launch_kernel<tl_decode_one_kernel<BF16, TG>>(
-        p, x, tokens, ldx, m, st, TdMember{G.codes[0], G.gather[0], G.alpha[0], G.mu[0], G.bias[0], G.n[0], G.B[0]},
-        G.y[0], G.ldy[0]);
-  else
+  const TdMember one{G.codes[0], G.gather[0], G.alpha[0], G.mu[0], G.bias[0], G.n[0], G.B[0]};
+  if constexpr (USE == TD_ONE && FX == TD_FX_NONE)
+    return td_launch_kernel<tl_decode_one_kernel<BF16, TG>>(p, x, tokens, ldx, m, st, one, G.y[0], G.ldy[0]);
+  else if constexpr (USE == TD_ONE)
+    return td_launch_kernel<tl_decode_one_fused_kernel<BF16, TG, FX>>(p, x, tokens, ldx, m, st, one, G.y[0], G.ldy[0],
+                                                                      p.X.nw, p.X.eps, p.X.res[0], p.X.ldr[0]);
+  else if constexpr (FX == TD_FX_NONE)
     return td_launch_kernel<tl_decode_kernel<BF16, TG, USE == TD_SWIGLU>>(p, x, tokens, ldx, m, st, G);
+  else
+    return td_launch_kernel<tl_decode_fused_kernel<BF16, TG, USE == TD_SWIGLU, FX>>(p, x, tokens, ldx, m, st, G, p.X);
 }
 
-template <bool BF16, TdUse USE>
+template <bool BF16, TdUse USE, TdFx FX>
 bool td_launch_tg(const TdPlan& p, const void* x, int tokens, int64_t ldx, int m, hipStream_t st) {
   if constexpr (USE != TD_SWIGLU) {  // never SWIGLU: four tokens' two gathered images alone are TD_LDS_PLAIN
-    if (p.TG == 4) return td_launch_as<BF16, 4, USE>(p, x, tokens, ldx, m, st);
+    if (p.TG == 4) return td_launch_as<BF16, 4, USE, FX>(p, x, tokens, ldx, m, st);
   }
-  return p.TG == 2 ? td_launch_as<BF16, 2, USE>(p, x, tokens, ldx, m, st)
-                   : td_launch_as<BF16, 1, USE>(p, x, tokens, ldx, m, st);
+  return p.TG == 2 ? td_launch_as<BF16, 2, USE, FX>(p, x, tokens, ldx, m, st)
+                   : td_launch_as<BF16, 1, USE, FX>(p, x, tokens, ldx, m, st);
 }
 
-template <TdUse USE>
+template <TdUse USE, TdFx FX = TD_FX_NONE>
 int td_launch(const TdPlan& p, const void* x, int tokens, int64_t ldx, int m, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  const bool ok = p.bf16 ? td_launch_tg<true, USE>(p, x, tokens, ldx, m, st)
-                         : td_launch_tg<false, USE>(p, x, tokens, ldx, m, st);
+  const bool ok = p.bf16 ? td_launch_tg<true, USE, FX>(p, x, tokens, ldx, m, st)
+                         : td_launch_tg<false, USE, FX>(p, x, tokens, ldx, m, st);
   if (!ok) {
     (void)hipGetLastError();
     return PT2Q_E_UNSUPPORTED;
@@ -620,7 +817,7 @@ extern "C" int pt2q_ternary_decode_group(const void* x, int xdtype, int tokens, 
                                          int epilogue, void* stream) {
   TdPlan p;
   const int rc = td_plan(x, xdtype, tokens, ldx, m, count, n, codes, gather, alpha, mu, B, bs, bias, y, ydtype, ldy,
-                         epilogue, p);
+                         epilogue, nullptr, 0.0f, nullptr, nullptr, p);
   if (rc != PT2Q_OK) return rc;
   return p.swiglu ? td_launch<TD_SWIGLU>(p, x, tokens, ldx, m, stream) : td_launch<TD_GROUP>(p, x, tokens, ldx, m, stream);
 }
@@ -632,6 +829,46 @@ extern "C" int pt2q_ternary_decode(const void* x, int xdtype, int tokens, int64_
                                    int ydtype, int64_t ldy, void* stream) {
   TdPlan p;
   const int rc = td_plan(x, xdtype, tokens, ldx, m, 1, &n, &codes, &gather, &alpha, &mu, &B, bs, &bias, &y, ydtype, &ldy,
-                         PT2Q_DECODE_PLAIN, p);
+                         PT2Q_DECODE_PLAIN, nullptr, 0.0f, nullptr, nullptr, p);
   return rc != PT2Q_OK ? rc : td_launch<TD_ONE>(p, x, tokens, ldx, m, stream);
+}
+
+// The group entry with the RMSNorm prologue and the residual epilogue.  A call that asks for
+// neither launches what pt2q_ternary_decode_group launches; a PLAIN group of one with either takes
+// its member and extras as plain kernel arguments, as pt2q_ternary_decode does.
+extern "C" int pt2q_ternary_decode_fused(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                                         const int* n, const uint8_t* const* codes, const int* const* gather,
+                                         const float* const* alpha, const float* const* mu, const int* B, int bs,
+                                         const float* const* bias, void* const* y, int ydtype, const int64_t* ldy,
+                                         int epilogue, const void* norm_weight, float norm_eps,
+                                         const void* const* residual, const int64_t* ldr, void* stream) {
+  TdPlan p;
+  const int rc = td_plan(x, xdtype, tokens, ldx, m, count, n, codes, gather, alpha, mu, B, bs, bias, y, ydtype, ldy,
+                         epilogue, norm_weight, norm_eps, residual, ldr, p);
+  if (rc != PT2Q_OK) return rc;
+  if (p.swiglu)
+    return p.fx == TD_FX_NORM ? td_launch<TD_SWIGLU, TD_FX_NORM>(p, x, tokens, ldx, m, stream)
+                              : td_launch<TD_SWIGLU>(p, x, tokens, ldx, m, stream);
+  if (p.fx == TD_FX_NONE) return td_launch<TD_GROUP>(p, x, tokens, ldx, m, stream);
+  if (count == 1)
+    return p.fx == TD_FX_NORM ? td_launch<TD_ONE, TD_FX_NORM>(p, x, tokens, ldx, m, stream)
+                              : td_launch<TD_ONE, TD_FX_RES>(p, x, tokens, ldx, m, stream);
+  return p.fx == TD_FX_NORM ? td_launch<TD_GROUP, TD_FX_NORM>(p, x, tokens, ldx, m, stream)
+                            : td_launch<TD_GROUP, TD_FX_RES>(p, x, tokens, ldx, m, stream);
+}
+
+extern "C" int pt2q_rmsnorm(const void* x, int xdtype, int tokens, int64_t ldx, int m, const void* weight, float eps,
+                            void* y, int64_t ldy, void* stream) {
+  if (!x || !weight || !y || tokens <= 0 || m <= 0 || ldx < m || ldy < m || !(eps >= 0.0f && eps <= FLT_MAX))
+    return PT2Q_E_ARG;
+  if (xdtype != PT2Q_F16 && xdtype != PT2Q_BF16) return PT2Q_E_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  if (xdtype == PT2Q_BF16)
+    hipLaunchKernelGGL(tl_rmsnorm_kernel<true>, dim3((unsigned)tokens), dim3(TD_THREADS), 0, st, (const uint16_t*)x,
+                       (long)ldx, m, (const uint16_t*)weight, eps, (uint16_t*)y, (long)ldy);
+  else
+    hipLaunchKernelGGL(tl_rmsnorm_kernel<false>, dim3((unsigned)tokens), dim3(TD_THREADS), 0, st, (const uint16_t*)x,
+                       (long)ldx, m, (const uint16_t*)weight, eps, (uint16_t*)y, (long)ldy);
+  PT2Q_LAUNCH_CHECK();
+  return PT2Q_OK;
 }

@@ -7,7 +7,9 @@ pt2q_ternary_linear (csrc/ternary_linear.hip): 2-bit packed codes dequantised in
 f16/bf16 MFMA operands; decode="fused" sends calls of 1..decode_max_tokens tokens to the
 single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead; linears that read the
 same x go through pt2q_ternary_decode_group (the same kernel) in one launch, a gated MLP's gate
-and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp).
+and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp);
+the decode calls take an RMSNorm as prologue and a residual add as epilogue inside the same launch
+(norm=, residual=, pt2q_ternary_decode_fused; rms_norm; TernaryMLPBlock).
 Two semantics:
 
   compat=False (default)  y = x · Ŵᵀ + b with the correct reconstruction of gptq.py:201-230
@@ -42,6 +44,16 @@ decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), DECODE
 # crossover is 1.  A caller whose shapes do better may raise it, up to the cap.
 MLP_DECODE_CROSSOVER_TOKENS = 1
 mlp_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), MLP_DECODE_CROSSOVER_TOKENS)
+# Largest token count a TernaryMLPBlock whose projections are decode="fused" runs in two launches
+# (norm prologue, residual epilogue); above it the block is rms_norm, the TernaryGatedMLP and
+# torch's add.  profiles/ternary_block_timing.txt has the two launches below that four-launch form
+# by 3.3-6.6 us at 1, 2 and 4 tokens at every measured shape and dtype and level with it or behind
+# at 8 (-0.5 .. +1.4 us), so the crossover is 4.  The table's four-launch form has
+# the TernaryGatedMLP on its own two-launch path, so the block also stays within
+# mlp_decode_max_tokens: above that the MLP goes through its children, which the table does not
+# cover, and the block follows it.  A caller whose shapes do better may raise both, up to the cap.
+BLOCK_DECODE_CROSSOVER_TOKENS = 4
+block_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), BLOCK_DECODE_CROSSOVER_TOKENS)
 
 
 def _check_mode(decode):
@@ -50,20 +62,65 @@ def _check_mode(decode):
     return decode
 
 
+def rms_norm(x: torch.Tensor, weight: torch.Tensor, eps: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pt2q_rmsnorm: the Llama RMSNorm weight * (x.float() * rsqrt(mean(x²) + eps)).to(x.dtype) over
+    the last dimension, bit-defined by contract RMSNORM16 (not torch's bits: its
+    reduction order and rsqrt differ).  x: fp16/bf16, tokens x m with unit column stride (any row
+    stride and base) or contiguous with more dimensions; weight: m elements of x's dtype; any
+    number of tokens; out: an optional tensor of x's shape and dtype to write into, which may be
+    x.  The norm= keyword of the decode calls computes the same bits inside their launch."""
+    what = "rms_norm"
+    _lib.require_device(x)
+    m = x.shape[-1] if x.dim() else 0
+    weight = _check_norm(x, (weight, eps), what)[0]
+    if x.dim() != 2 and not x.is_contiguous() or x.dim() == 2 and x.stride(1) != 1:
+        raise _lib.Pt2qError(f"{what}: x must be tokens x m with unit column stride, or contiguous")
+    if out is None:
+        out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    elif out.shape != x.shape or out.dtype != x.dtype or not out.is_cuda or \
+            (out.stride(1) != 1 if out.dim() == 2 else not out.is_contiguous()):
+        raise _lib.Pt2qError(f"{what}: out must have x's shape and dtype, with unit column stride or contiguous")
+    x2, o2 = (x, out) if x.dim() == 2 else (x.view(-1, m), out.view(-1, m))
+    tokens = x2.shape[0]
+    if tokens:
+        _lib.check(_lib.lib().pt2q_rmsnorm(
+            _lib.ptr(x2), _lib.dtype_code(x2), tokens, x2.stride(0) if tokens > 1 else m, m, _lib.ptr(weight), float(eps),
+            _lib.ptr(o2), o2.stride(0) if tokens > 1 else m, _lib.stream_of(x.device)), "pt2q_rmsnorm")
+    return out
+
+
+def _check_norm(x, norm, what):
+    """(weight, eps) of a norm= keyword after its checks."""
+    weight, eps = norm
+    _lib.require_device(weight)
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.dim() < 1 or weight.dtype != x.dtype or \
+            weight.dim() != 1 or weight.numel() != x.shape[-1]:
+        raise _lib.Pt2qError(f"{what}: the norm weight has x's dtype (fp16 / bf16) and its m elements")
+    return weight.contiguous(), float(eps)
+
+
 def ternary_decode(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, alpha: torch.Tensor,
                    mu: torch.Tensor, block_size: int, bias: Optional[torch.Tensor] = None,
-                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+                   norm=None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pt2q_ternary_decode: y = x · Ŵᵀ (+ bias) for 1..8 tokens in one launch, bit-defined (DESIGN.md
     §3 DOT64P).  x: tokens x m fp16/bf16 with unit column stride (any row stride and base); codes
     (n x P/4 uint8) and gather (P int32) from pt2q_ternary_pack; alpha, mu: n x B fp32; bias: n fp32
     or None; out_dtype: x's dtype (default) or torch.float32; out: an optional tokens x n tensor of
-    that dtype with unit column stride to write into."""
+    that dtype with unit column stride to write into.  norm=(weight, eps): the layer reads
+    rms_norm(x, weight, eps), computed inside the launch; residual: a tokens x n tensor of x's
+    dtype added to the result as torch adds 16-bit tensors (RESADD16), which may be `out` itself.
+    With either the call is pt2q_ternary_decode_fused, still one launch."""
     what = "ternary_decode"
     packs, bs = _group_members(x, [(codes, gather, alpha, mu, bias)], block_size, what)
     codes, gather, alpha, mu, bias = packs[0]
     tokens, m = x.shape
     n, B = alpha.shape
     out = _check_out(out, tokens, n, x.dtype if out_dtype is None else out_dtype, x.device, what)
+    if norm is not None or residual is not None:
+        if tokens:
+            _decode_group(x, packs, bs, [out], _lib.DECODE_PLAIN, "pt2q_ternary_decode_fused", norm, [residual], what)
+        return out
     if tokens == 0:
         return out
     ldx = x.stride(0) if tokens > 1 else m
@@ -114,18 +171,34 @@ def _group_members(x, members, block_size, what):
     return packs, int(block_size)
 
 
-def _decode_group(x, packs, block_size, outs, epilogue, what):
+def _decode_group(x, packs, block_size, outs, epilogue, what, norm=None, residuals=None, caller=None):
+    """pt2q_ternary_decode_group, or with norm (weight, eps) or residuals (one tensor or None per
+    out) pt2q_ternary_decode_fused."""
     tokens, m = x.shape
     count = len(packs)
     ns = (ctypes.c_int * count)(*[p[2].shape[0] for p in packs])
     Bs = (ctypes.c_int * count)(*[p[2].shape[1] for p in packs])
-    ldys = (ctypes.c_int64 * len(outs))(*[o.stride(0) if tokens > 1 else o.shape[1] for o in outs])
+    ld = lambda ts: (ctypes.c_int64 * len(ts))(*[0 if t is None else t.stride(0) if tokens > 1 else t.shape[1] for t in ts])  # noqa: E731
+    ldys = ld(outs)
     arrs = [_lib.ptr_array([p[i] for p in packs]) for i in range(5)] + [_lib.ptr_array(outs)]
     as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
-    _lib.check(_lib.lib().pt2q_ternary_decode_group(
-        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns),
-        arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0],
-        _lib.dtype_code(outs[0]), as_p(ldys), epilogue, _lib.stream_of(x.device)), what)
+    args = (_lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns),
+            arrs[0][0], arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0],
+            _lib.dtype_code(outs[0]), as_p(ldys), epilogue)
+    if norm is None and residuals is None:
+        _lib.check(_lib.lib().pt2q_ternary_decode_group(*args, _lib.stream_of(x.device)), what)
+        return
+    weight, eps = (None, 0.0) if norm is None else _check_norm(x, norm, caller)
+    residuals = [None] * len(outs) if residuals is None else list(residuals)
+    if len(residuals) != len(outs):
+        raise _lib.Pt2qError(f"{caller}: one residual (or None) per output")
+    for r, o in zip(residuals, outs):
+        if r is not None and (not isinstance(r, torch.Tensor) or not r.is_cuda or r.shape != o.shape or
+                              r.dtype != o.dtype or r.stride(1) != 1):
+            raise _lib.Pt2qError(f"{caller}: a residual has its output's shape and dtype, with unit column stride")
+    res, ldrs = _lib.ptr_array(residuals), ld(residuals)
+    _lib.check(_lib.lib().pt2q_ternary_decode_fused(*args, _lib.ptr(weight), eps, res[0], as_p(ldrs),
+                                                    _lib.stream_of(x.device)), what)
 
 
 def _check_out(out, tokens, n, dtype, device, what):
@@ -137,13 +210,14 @@ def _check_out(out, tokens, n, dtype, device, what):
 
 
 def ternary_decode_group(x: torch.Tensor, members, out_dtype: Optional[torch.dtype] = None, outs=None,
-                         block_size: Optional[int] = None):
+                         block_size: Optional[int] = None, norm=None, residuals=None):
     """pt2q_ternary_decode_group, PLAIN: 1..4 ternary linears on the same x (1..8 tokens) in one
     launch -- the q/k/v projections of a host that owns its attention code.  members: TernaryLinear
     modules (packed on demand) or (codes, gather, alpha, mu, bias) tuples as ternary_decode takes
     them, then with block_size.  Returns one tokens x n tensor per member (out_dtype: x's dtype or
     torch.float32; outs: optional tensors to write into), each bit-equal to ternary_decode on that
-    member alone."""
+    member alone.  norm=(weight, eps) and residuals (one tensor or None per member) as in
+    ternary_decode: input_layernorm and q/k/v in one launch."""
     what = "ternary_decode_group"
     packs, bs = _group_members(x, members, block_size, what)
     tokens = x.shape[0]
@@ -152,24 +226,29 @@ def ternary_decode_group(x: torch.Tensor, members, out_dtype: Optional[torch.dty
         raise _lib.Pt2qError(f"{what}: one out per member")
     outs = [_check_out(None if outs is None else outs[z], tokens, p[2].shape[0], out_dtype, x.device, what)
             for z, p in enumerate(packs)]
-    if tokens:
+    if tokens and norm is None and residuals is None:
         _decode_group(x, packs, bs, outs, _lib.DECODE_PLAIN, "pt2q_ternary_decode_group")
+    elif tokens:
+        _decode_group(x, packs, bs, outs, _lib.DECODE_PLAIN, "pt2q_ternary_decode_fused", norm, residuals, what)
     return outs
 
 
 def ternary_decode_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor] = None,
-                          block_size: Optional[int] = None) -> torch.Tensor:
+                          block_size: Optional[int] = None, norm=None) -> torch.Tensor:
     """pt2q_ternary_decode_group, SWIGLU: h = silu(gate(x)) * up(x) for 1..8 tokens in one launch,
     bit-defined by contract SWIGLU16 from the outputs the two separate
     ternary_decode calls would give.  gate, up: members as in ternary_decode_group, equal widths;
-    h has x's dtype."""
+    h has x's dtype.  norm=(weight, eps) as in ternary_decode: post_attention_layernorm, gate, up
+    and the activation in one launch."""
     what = "ternary_decode_swiglu"
     packs, bs = _group_members(x, [gate, up], block_size, what)
     if packs[0][2].shape[0] != packs[1][2].shape[0]:
         raise _lib.Pt2qError(f"{what}: gate and up have the same number of rows")
     out = _check_out(out, x.shape[0], packs[0][2].shape[0], x.dtype, x.device, what)
-    if x.shape[0]:
+    if x.shape[0] and norm is None:
         _decode_group(x, packs, bs, [out], _lib.DECODE_SWIGLU, "pt2q_ternary_decode_group")
+    elif x.shape[0]:
+        _decode_group(x, packs, bs, [out], _lib.DECODE_SWIGLU, "pt2q_ternary_decode_fused", norm, None, what)
     return out
 
 
@@ -319,6 +398,42 @@ class TernaryGatedMLP(nn.Module):
                 y = ternary_decode(h, codes, gather, a32, m32, down.block_size, b32)
                 return y.reshape(*x.shape[:-1], down.out_features)
         return down(F.silu(gate(x)) * up(x))
+
+
+class TernaryMLPBlock(nn.Module):
+    """forward(h) = h + mlp(rms_norm(h, norm_weight, eps)): the MLP half of a pre-norm decoder layer
+    over a TernaryGatedMLP.  With all three projections at decode="fused", h in their dtype and
+    1..min(block_decode_max_tokens, mlp_decode_max_tokens) tokens it takes two launches --
+    ternary_decode_swiglu with the norm as prologue, then ternary_decode on down_proj with h as
+    residual -- in place of four (rms_norm, SwiGLU, down_proj, torch's add), with the same bits;
+    every other call is the formula above over the same modules.
+    norm_weight (hidden elements of the projections' dtype) is a buffer: state_dict key
+    "norm_weight", beside the children's keys under "mlp."."""
+
+    def __init__(self, norm_weight: torch.Tensor, eps: float, mlp: TernaryGatedMLP):
+        super().__init__()
+        if not isinstance(mlp, TernaryGatedMLP) or mlp.down_proj.out_features != mlp.gate_proj.in_features:
+            raise _lib.Pt2qError("TernaryMLPBlock: mlp is a TernaryGatedMLP whose down_proj returns to the hidden width")
+        if norm_weight.dim() != 1 or norm_weight.numel() != mlp.gate_proj.in_features or \
+                norm_weight.dtype != mlp.gate_proj.dtype:
+            raise _lib.Pt2qError("TernaryMLPBlock: norm_weight has the hidden width and the projections' dtype")
+        self.register_buffer("norm_weight", norm_weight.detach().clone().to(mlp.gate_proj.T.device))
+        self.eps = float(eps)
+        self.mlp = mlp
+
+    def forward(self, h: torch.Tensor) -> torch.Tensor:
+        gate, up, down = self.mlp.gate_proj, self.mlp.up_proj, self.mlp.down_proj
+        hidden = gate.in_features
+        if gate.decode == up.decode == down.decode == "fused" and h.dtype == gate.dtype == self.norm_weight.dtype:
+            ht = h.reshape(-1, hidden).contiguous()
+            if 0 < ht.shape[0] <= min(block_decode_max_tokens, mlp_decode_max_tokens):
+                if down._packed is None:
+                    down._prepare()
+                a = ternary_decode_swiglu(ht, gate, up, norm=(self.norm_weight, self.eps))
+                codes, gather, a32, m32, b32 = down._packed
+                y = ternary_decode(a, codes, gather, a32, m32, down.block_size, b32, residual=ht)
+                return y.reshape(h.shape)
+        return h + self.mlp(rms_norm(h.contiguous(), self.norm_weight.to(h.dtype), self.eps))
 
 
 def _gated_mlp_matches(gate, up, down) -> bool:
