@@ -395,7 +395,11 @@ int pt2q_launch_cholesky_inverse(const float* H, long ldh, int m, float* Hinv, l
       PT2Q_LAUNCH_CHECK();
     }
     const int rest = m - p0 - nb;
-    if (nb == NB) {  // whole blocks: one lane per column / row
+    // whole blocks: one lane per column / row.  lane_stage_block reads the diagonal block with
+    // float4 loads at U + p0 * ld + r * ld + 4 * c4 (ld == m, item bases m * m floats apart): 16-byte
+    // aligned only for m % 4 == 0.  Any other width takes the four-lanes-per-row kernel below, whose
+    // loads are scalar and whose chains take the same terms in the same order (same bits).
+    if (nb == NB && m % 4 == 0) {
       const int npanel = rest > 0 ? (int)ceil_div((long)rest, 256) : 0;
       const int ninv = (int)ceil_div((long)(p0 + nb), 256);
       hipLaunchKernelGGL(chol_panel_trtri_lane_kernel, dim3(npanel + ninv, batch), dim3(256), 0, st, U, ld, p0, m,

@@ -483,12 +483,13 @@ def quantize_unit(Ws, X: Optional[torch.Tensor] = None, G: Optional[torch.Tensor
 
 
 def _unit_tail(Ws, Gm, nsamples, ws, statuses, X, G, block_size, use_ssr, percdamp, max_iter, t_dtype,
-               Hinv=None, info=None):
+               Hinv=None, info=None, s1d=None):
     """Damping, Cholesky inverse and every weight's block loop of a unit whose raw Gram is Gm,
     on the current stream; returns the deferred UnitRun.  With Hinv (and its device info word)
     given -- an item of hessian_inverse_batched -- only the block loops run.  The pinv redo
     rebuilds the Gram from the caller's X (or G): Gm may be a reused buffer by the time the
-    status is read."""
+    status is read.  s1d (per-channel only, as quantize_blocks): S1 then d of Gm, formed already;
+    Gm is then not read, so it may hold its upper triangle alone."""
     m, dev = Ws[0].shape[1], Ws[0].device
     L = _lib.lib()
     st = _lib.stream_of(dev)
@@ -504,6 +505,13 @@ def _unit_tail(Ws, Gm, nsamples, ws, statuses, X, G, block_size, use_ssr, percda
     elif info is None:
         raise ValueError("_unit_tail: a given Hinv needs its info word")
     flags = (_lib.FLAG_SSR if use_ssr else 0) | _lib.AGA_ACT
+    A = Gm
+    if s1d is not None:
+        if needs_inverse(m, block_size) or m <= 512 or s1d.numel() != m + 1:
+            raise ValueError("_unit_tail: s1d is for one-block (per-channel) loops with m > 512, m + 1 floats")
+        if s1d.dtype != torch.float32 or not s1d.is_contiguous() or s1d.device != dev:
+            raise ValueError("_unit_tail: s1d must be a contiguous fp32 tensor on W's device")
+        A, flags = s1d, flags | _lib.FLAG_S1_GIVEN
     outs = []
     for W in Ws:
         n = W.shape[0]
@@ -515,7 +523,7 @@ def _unit_tail(Ws, Gm, nsamples, ws, statuses, X, G, block_size, use_ssr, percda
                           torch.zeros(B, dtype=torch.int32, device=dev))
         bws = ws.blocks(n)
         rc = L.pt2q_quantize_blocks(
-            _lib.ptr(W), _lib.dtype_code(W), m, n, m, int(block_size), flags, _lib.ptr(Gm), m,
+            _lib.ptr(W), _lib.dtype_code(W), m, n, m, int(block_size), flags, _lib.ptr(A), m,
             _lib.ptr(Hinv), m, int(max_iter), _lib.ptr(out.alpha), _lib.ptr(out.mu), _lib.ptr(out.T),
             _lib.dtype_code(out.T), _lib.ptr(out.perm), _lib.ptr(out.iters), _lib.ptr(bws), bws.numel(), st)
         _lib.check(rc, "pt2q_quantize_blocks")
@@ -578,10 +586,12 @@ class UnitPipeline:
 
     def run(self, Ws, X: Optional[torch.Tensor] = None, G: Optional[torch.Tensor] = None,
             nsamples: Optional[int] = None, Hinv: Optional[torch.Tensor] = None,
-            info: Optional[torch.Tensor] = None):
+            info: Optional[torch.Tensor] = None, s1d: Optional[torch.Tensor] = None):
         """Issue one unit: its Gram from X, or -- with G (a raw Gram over nsamples rows, e.g. a
         GramAccumulator's, read in place and not modified) -- its tail alone; with Hinv and info
-        as well (an item of hessian_inverse_batched), only its block loops."""
+        as well (an item of hessian_inverse_batched), only its block loops.  s1d (with G,
+        per-channel only): S1 then d of G formed already (s1_from_gram_batched's row); G itself is
+        then not read."""
         Ws = [_float_input(W) for W in Ws]
         if X is not None:
             X = _float_input(X.reshape(-1, X.shape[-1]))
@@ -598,7 +608,7 @@ class UnitPipeline:
             if G is not None:
                 G = G.contiguous().float()
                 run = _unit_tail(Ws, G, N, ws, [], X, G, self.bs, self.use_ssr, self.percdamp,
-                                 self.max_iter, torch.int8, Hinv=Hinv, info=info)
+                                 self.max_iter, torch.int8, Hinv=Hinv, info=info, s1d=s1d)
                 run.join = self.join
                 return run
             if self.gram_done is not None:

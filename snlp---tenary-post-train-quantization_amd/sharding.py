@@ -725,6 +725,11 @@ class GramsFirst:
                 self._wait_inverse(torch.cuda.current_stream(self.dev), key)
                 return self.pipe.run(Ws, G=grp["G"][z], nsamples=nsamples, Hinv=grp["Hinv"][z],
                                      info=grp["info"][z:z + 1])
+            if self.batched and grp.get("S1d") is not None:
+                # per-channel: the loop takes the S1 / d inverses() formed, as tails()'s "one" loops
+                # do -- the Gram itself may hold its upper triangle alone (flush())
+                self._wait_inverse(torch.cuda.current_stream(self.dev), key)
+                return self.pipe.run(Ws, G=grp["G"][z], nsamples=nsamples, s1d=grp["S1d"][z])
             return self.pipe.run(Ws, G=grp["G"][z], nsamples=nsamples)
         return self.pipe.run(Ws, G=self.G[key], nsamples=nsamples)
 

@@ -172,20 +172,41 @@ def _units_and_data(pt2q, specs, seed):
     return units, data
 
 
-@pytest.mark.parametrize("bs,batched", [(1024, True), (1 << 14, True), (1 << 14, False)])
-def test_grams_first_per_channel_equals_quantize_layer(pt2q, bs, batched):
+@pytest.mark.parametrize("bs,batched,group", [
+    pytest.param(1024, True, 16, id="1024-True"), pytest.param(1 << 14, True, 16, id="16384-True"),
+    pytest.param(1 << 14, False, 16, id="16384-False"),
+    pytest.param(1024, True, 1, id="1024-True-group1"), pytest.param(1 << 14, True, 1, id="16384-True-group1")])
+def test_grams_first_per_channel_equals_quantize_layer(pt2q, bs, batched, group):
     """the per-channel (block >= m, C5) grams-first step runs no Hessian inverse
     -- H^-1 feeds only the error feedback (main.py:198-214), which one block never reaches -- and
     its results equal pt2q_quantize_layer (which skips the inverse the same way) bit for bit:
     bf16 640 x 1024 linears, a shared-input unit of two, batched Grams, the per-linear block
-    loops issued on the lanes with their status read once at finish."""
+    loops issued on the lanes with their status read once at finish.
+
+    The step is driven by hand with every Gram slot filled with NaN first: a batched step writes
+    only the upper triangles (flush(): `upper`), so any loop that formed S1 / d from full rows of
+    such a Gram -- as group=1's tail() did before it took the formed S1 / d -- reads NaN."""
     import importlib
     sharding = importlib.import_module("pt2q.sharding")
     specs = [(1024, (640, 512), 4096, torch.bfloat16), (1024, (640,), 4096, torch.bfloat16)]
     units, data = _units_and_data(pt2q, specs, 1200)
     pipe = pt2q.UnitPipeline("cuda", bs, True, lanes=3)
-    gf = sharding.GramsFirst(pipe, "cuda", batched=batched)
-    res, _ = sharding.quantize_units_sharded(units, lambda u: data[u[0]], pack=False, grams_first=gf)
+    gf = sharding.GramsFirst(pipe, "cuda", batched=batched, group=group)
+    gf.begin([(i, u[1][0][2], u[2]) for i, u in enumerate(units)])
+    for grp in gf.groups.values():
+        grp["G"].fill_(float("nan"))
+    for i, u in enumerate(units):
+        gf.gram(i, data[u[0]][0])
+    gf.flush()
+    assert all(grp["upper"] == batched for grp in gf.groups.values())  # batched: upper-only Grams
+    gf.inverses()
+    jobs = [(i, [data[u[0]][1][p] for p, _, _ in u[1]], u[2]) for i, u in enumerate(units)]
+    assert gf.grouped == (batched and group > 1)
+    runs = gf.tails(jobs) if gf.grouped else [gf.tail(i, Ws, N) for i, Ws, N in jobs]
+    outs = [r.finish() for r in runs]
+    gf.check()
+    res = {f"{u[0]}.{p}": {"alpha": o.alpha, "mu": o.mu, "T": o.T, "perm": o.perm}
+           for u, uo in zip(units, outs) for (p, _, _), o in zip(u[1], uo)}
     assert gf.groups and all(grp["Hinv"] is None for grp in gf.groups.values())  # no inverse buffer
     assert not gf.inv_done and not gf.scratch  # ... and no batched factorisation ran
     for name, lins, _ in units:
