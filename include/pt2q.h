@@ -236,7 +236,9 @@ int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n, int m, co
 /* One ATQ stage on W (n x b, row-major fp32, leading dim ldw) (quantizer.py:32-293).
  * alpha, mu: n fp32 (in for ROUND/ITF, out otherwise); T: n x b fp32, leading dim ldt
  * (in for GRID/ITF/AGA, out for INIT/ROUND/ITF/FULL); S1 (b) and d_dev (1) for AGA/FULL
- * (NULL S1 in FULL = no activations).  iters_dev (nullable) receives ITF iterations. */
+ * (NULL S1 in FULL = no activations).  iters_dev (nullable) receives ITF iterations.
+ * max_iter (quantizer.py:25,162) caps the ITF rounds of ITF/FULL: 0 returns the init grid and
+ * codes; a negative cap is PT2Q_E_ARG in every mode, as in every entry that takes one. */
 int pt2q_atq_stage(int mode, const float* W, int64_t ldw, int n, int b, float* alpha, float* mu,
                    float* T, int64_t ldt, const float* S1, const float* d_dev, int max_iter,
                    int* iters_dev, void* workspace, size_t workspace_bytes, void* stream);

@@ -755,7 +755,8 @@ extern "C" int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n
                                    void* stream) {
   hipStream_t st = (hipStream_t)stream;
   if (!W || !X || !info_dev || N <= 0 || N > INT_MAX || m <= 0 || n <= 0 || b <= 0 ||
-      !dtype_ok(xdtype) || !dtype_ok(wdtype) || ldx < m || ldw < m || (flags & PT2Q_FLAG_S1_GIVEN))
+      !dtype_ok(xdtype) || !dtype_ok(wdtype) || ldx < m || ldw < m || (flags & PT2Q_FLAG_S1_GIVEN) ||
+      max_iter < 0)
     return PT2Q_E_ARG;
   Carve c{(char*)workspace, workspace_bytes};
   int rc;

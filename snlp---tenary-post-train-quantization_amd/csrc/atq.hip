@@ -1331,7 +1331,7 @@ extern "C" int pt2q_atq_stage(int mode, const float* W, int64_t ldw, int n, int 
                               const float* d_dev, int max_iter, int* iters_dev, void* workspace,
                               size_t workspace_bytes, void* stream) {
   hipStream_t st = (hipStream_t)stream;
-  if (n <= 0 || b <= 0 || !W || !alpha || !mu || !T || ldw < b || ldt < b) return PT2Q_E_ARG;
+  if (n <= 0 || b <= 0 || !W || !alpha || !mu || !T || ldw < b || ldt < b || max_iter < 0) return PT2Q_E_ARG;
   if ((mode == PT2Q_STAGE_AGA) && (!S1 || !d_dev)) return PT2Q_E_ARG;
   if ((mode == PT2Q_STAGE_ITF || mode == PT2Q_STAGE_FULL) &&
       (!workspace || workspace_bytes < sizeof(int)))

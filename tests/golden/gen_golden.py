@@ -608,10 +608,38 @@ def gen_ppl():
          nlin=len(params), **kw)
 
 
+def gen_itf_cap():
+    """The ITF iteration cap (quantizer.py:25,162): AsymmetricTernaryQuantizer(max_iter=c) for
+    c in {0, 1, 2, 3} and the default 100, on a 64 x 128 and a 37 x 640 block -- quantize(W, X)
+    (the AGA after a capped ITF) and iterative_ternary_fitting from the reference's own init.  A
+    capped loop returns the grid of the codes before its last round with the codes after it."""
+    print("ITF iteration cap (quantizer.py:136-175 at max_iter < its natural count)")
+    kw = {"caps": np.array([0, 1, 2, 3, 100])}
+    for tag, (n, b, N) in (("a", (64, 128, 48)), ("b", (37, 640, 24))):
+        W = torch.from_numpy(synth.weights(140 + n, n, b))
+        X = torch.from_numpy(synth.activations(240 + b, N, b))
+        a0, m0, T0 = rq.AsymmetricTernaryQuantizer().ternary_init(W)
+        kw.update({f"{tag}_W": W.numpy(), f"{tag}_X": X.numpy(), f"{tag}_a_init": a0.numpy().ravel(),
+                   f"{tag}_m_init": m0.numpy().ravel(), f"{tag}_T_init": T0.numpy().astype(np.int8)})
+        codes = []
+        for c in kw["caps"]:
+            atq = rq.AsymmetricTernaryQuantizer(max_iter=int(c))
+            a1, m1, T1 = atq.iterative_ternary_fitting(W, a0, m0, T0)
+            af, mf, Tf = atq.quantize(W, X)
+            an, mn, Tn = atq.quantize(W)
+            assert torch.equal(Tf, T1) and torch.equal(Tn, T1) and torch.equal(an, a1) and torch.equal(mn, m1)
+            codes.append(T1)
+            kw.update({f"{tag}_a_itf{c}": a1.numpy().ravel(), f"{tag}_m_itf{c}": m1.numpy().ravel(),
+                       f"{tag}_T{c}": T1.numpy().astype(np.int8), f"{tag}_a_aga{c}": af.numpy().ravel(),
+                       f"{tag}_m_aga{c}": mf.numpy().ravel()})
+        assert torch.equal(codes[0], T0) and all(not torch.equal(x, y) for x, y in zip(codes, codes[1:]))
+    save("atq_itf_cap", **kw)
+
+
 GENERATORS = {"layers": gen_layers, "atq": gen_atq, "ssr": gen_ssr, "hessian": gen_hessian, "hessian512": gen_hessian512,
               "trace": gen_trace, "examples": gen_examples, "wide": gen_wide,
               "ternary": gen_ternary, "fp16": gen_fp16, "loop16": gen_loop16,
-              "model": gen_model, "model_tf": gen_model_tf, "ppl": gen_ppl}
+              "model": gen_model, "model_tf": gen_model_tf, "ppl": gen_ppl, "itf_cap": gen_itf_cap}
 
 if __name__ == "__main__":
     # `python gen_golden.py [group ...]` regenerates only the named groups (default: all)

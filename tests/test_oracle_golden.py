@@ -198,6 +198,42 @@ def test_atq_edge_cases():
     np.testing.assert_allclose(m.ravel(), g["grid_mu"], atol=SCALE_TOL, rtol=0)
 
 
+@pytest.mark.parametrize("tag,n,b", [("a", 64, 128), ("b", 37, 640)])
+def test_atq_itf_cap(tag, n, b):
+    """The ITF iteration cap (quantizer.py:25,162) at 0, 1, 2, 3 and the default 100: the oracle's
+    loop (orc_itf) leaves by the cap as the reference's does -- the codes of the last round with the
+    grid of the codes before it -- in iterative_ternary_fitting from the reference's own init
+    (teacher forcing) and in quantize with and without activations (the AGA after a capped ITF)."""
+    g = load_golden("atq_itf_cap")
+    W, X = g[f"{tag}_W"], g[f"{tag}_X"]
+    assert W.shape == (n, b) and list(g["caps"]) == [0, 1, 2, 3, 100]
+    np.testing.assert_array_equal(orc.ternary_init(W)[2].astype(np.int8), g[f"{tag}_T_init"])
+    its = []
+    for c in g["caps"]:
+        a1, m1, T1, it = orc.iterative_ternary_fitting(W, g[f"{tag}_a_init"], g[f"{tag}_m_init"],
+                                                       g[f"{tag}_T_init"].astype(np.float32), max_iter=int(c))
+        np.testing.assert_array_equal(T1.astype(np.int8), g[f"{tag}_T{c}"])
+        np.testing.assert_allclose(a1.ravel(), g[f"{tag}_a_itf{c}"], atol=SCALE_TOL, rtol=0)
+        np.testing.assert_allclose(m1.ravel(), g[f"{tag}_m_itf{c}"], atol=SCALE_TOL, rtol=0)
+        an, mn, Tn, itn = orc.atq_quantize(W, max_iter=int(c))
+        np.testing.assert_array_equal(Tn.astype(np.int8), g[f"{tag}_T{c}"])
+        np.testing.assert_allclose(an.ravel(), g[f"{tag}_a_itf{c}"], atol=SCALE_TOL, rtol=0)
+        np.testing.assert_allclose(mn.ravel(), g[f"{tag}_m_itf{c}"], atol=SCALE_TOL, rtol=0)
+        af, mf, Tf, itf = orc.atq_quantize(W, X, max_iter=int(c))
+        np.testing.assert_array_equal(Tf.astype(np.int8), g[f"{tag}_T{c}"])
+        check_scales(af.ravel(), g[f"{tag}_a_aga{c}"], "a_aga")
+        check_scales(mf.ravel(), g[f"{tag}_m_aga{c}"], "m_aga")
+        assert it == itn == itf
+        its.append(it)
+    assert its[:4] == [0, 1, 2, 3] and 5 <= its[4] < 100  # every cap below 100 cuts the loop
+    # ... and the fixture's capped results are not the uncapped one: codes change with every cap,
+    # and the grid of cap 0 is ternary_init's
+    codes = [g[f"{tag}_T{c}"] for c in g["caps"]]
+    assert all(not np.array_equal(x, y) for x, y in zip(codes, codes[1:]))
+    np.testing.assert_array_equal(g[f"{tag}_a_itf0"], g[f"{tag}_a_init"])
+    np.testing.assert_array_equal(g[f"{tag}_m_itf0"], g[f"{tag}_m_init"])
+
+
 @pytest.mark.parametrize("name", ["ssr_4096x4096", "ssr_1024x1000_subset"])
 def test_ssr_select(name):
     import synth
