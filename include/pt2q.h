@@ -148,7 +148,8 @@ int pt2q_prepare_hessian(const float* G, int64_t ldg, int m, int64_t nsamples, f
 
 /* Hinv = cholesky_inverse(cholesky(H)) (main.py:136-139, gptq.py:101-103), full symmetric.
  * info_dev receives 0, or k+1 for the first non-positive pivot (then Hinv is undefined and the
- * caller applies torch.linalg.pinv, main.py:140-141). */
+ * caller applies torch.linalg.pinv, main.py:140-141).  For an H with non-finite entries only
+ * info_dev is defined (Hinv is not, even where info_dev is 0). */
 int pt2q_cholesky_inverse(const float* H, int64_t ldh, int m, float* Hinv, int64_t ldhi,
                           void* workspace, size_t workspace_bytes, int* info_dev, void* stream);
 

@@ -154,6 +154,12 @@ def test_entry_on_a_delayed_stream(pt2q, cycles_per_ms, case):
     # work issued on the wrong stream -- stream 0, say -- is ordered by accident when that stream
     # shares s's queue.  It cannot share both.
     for s in (torch.cuda.Stream(), torch.cuda.Stream()):
+        # The caching allocator keeps one pool per stream: the clones taken behind the sleep would be
+        # the first blocks of s's pool, i.e. device allocations (milliseconds each for the larger
+        # outputs, and of no fixed cost) inside the timed window.  Take and drop them once before the
+        # sleep, so that the window holds the enqueue alone.
+        with torch.cuda.stream(s):
+            snapshot(case, B)
         sleep_on(s, delay, cycles_per_ms)
         woke = torch.cuda.Event()
         woke.record(s)
