@@ -195,17 +195,9 @@ int hess_block_s1(const float* A, long lda, const int* blk, int bs, BlockWs& w, 
   return pt2q_launch_aga_s1(1, w.hS, bs, nullptr, bs, w.S1, w.d, st);
 }
 
-// per-channel setup in one launch: perm = [0, m) (the block is every column in ascending order),
-// the wide ATQ's counters (2 ints) and the iteration count zeroed -- instead of two memsets and a
-// select_seq launch per linear
-__global__ void pc_setup_kernel(int64_t* perm, int m, int* counters, int* iters) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < m) perm[i] = i;
-  if (i < 2) counters[i] = 0;
-  if (i == 0) *iters = 0;
-}
-
-// the grouped per-channel setup (pc_setup_kernel per linear z = blockIdx.y)
+// per-channel setup in one launch, linear z = blockIdx.y: perm = [0, m) (the block is every column
+// in ascending order), the wide ATQ's counters (2 ints) and the iteration count zeroed -- instead
+// of two memsets and a select_seq launch per linear
 struct PcSetupGroup {
   int64_t* perm[PT2Q_PC_GROUP_MAX];
   int* counters[PT2Q_PC_GROUP_MAX];
@@ -228,125 +220,28 @@ __global__ void i32_to_i64_kernel(const int* a, int n, int64_t* b) {
   if (i < n) b[i] = a[i];
 }
 
-int run_blocks(const void* W, int wdtype, long ldw_in, int n, int m, int b, int flags,
-               const float* A, long lda, const float* Hinv, long ldhi, int max_iter, float* alpha,
-               float* mu, void* T, int tdtype, int64_t* perm, int* iters_dev, BlockWs& w,
-               hipStream_t st) {
-  int rc;
-  const int B = b < m ? ceil_div(m, b) : 1;
-  const bool ssr = (flags & PT2Q_FLAG_SSR) != 0;
-  const int aga = flags & PT2Q_AGA_MASK;
-  int* iters = iters_dev ? iters_dev : w.iters;
-  if (B == 1 && m > 512 && aga != PT2Q_AGA_HESS) {
-    // Per-channel (block_size >= m, main.py:176-189 with one block): the block is every column in
-    // ascending order -- SSR over the whole remaining set returns it in rem order, and rem is
-    // [0, m) -- so the wide ATQ reads the caller's row-major W in place (no feature-major copy, no
-    // code transpose) and writes T, alpha, mu (n x 1) straight into the outputs.
-    {
-      StageScope ts(PT2Q_TIMER_SETUP, st);
-      hipLaunchKernelGGL(pc_setup_kernel, dim3(ceil_div(m, 256)), dim3(256), 0, st, perm, m, w.counters, iters);
-      PT2Q_LAUNCH_CHECK();
-    }
-    StageScope ts_atq(PT2Q_TIMER_ATQ, st);
-    const bool act = aga == PT2Q_AGA_ACT;
-    // S1 / d given (PT2Q_FLAG_S1_GIVEN: A = S1 then d, formed once per Gram) or formed here
-    const bool given = act && (flags & PT2Q_FLAG_S1_GIVEN) != 0;
-    if (act && !given && (rc = pt2q_launch_aga_s1(1, A, lda, nullptr, m, w.S1, w.d, st)) != PT2Q_OK) return rc;
-    const float* S1 = given ? A : w.S1;
-    const float* dv = given ? A + m : w.d;
-    return pt2q_launch_atq_wide_rm(W, wdtype, ldw_in, n, m, act ? S1 : nullptr, dv, max_iter, alpha, mu, T,
-                                   tdtype, m, iters, w.counters, st);
+// Per-channel blocks (one block of every column, m > 512) of `count` linears: the setup, then the
+// wide ATQ on each caller's row-major W, writing T, alpha, mu (n x 1) straight into the outputs.
+int run_perchannel(int count, const PcLinear* lin, int wdtype, int m, int max_iter, int tdtype,
+                   hipStream_t st) {
+  PcSetupGroup sg{};
+  for (int z = 0; z < count; ++z) {
+    sg.perm[z] = lin[z].perm;
+    sg.counters[z] = lin[z].counters;
+    sg.iters[z] = lin[z].iters;
   }
   {
     StageScope ts(PT2Q_TIMER_SETUP, st);
-    // W (n x m) -> Wt (m x ldw, fp32)
-    if ((rc = pt2q_launch_transpose_to_f32(W, wdtype, ldw_in, n, m, w.Wt, w.ldw, st)) != PT2Q_OK)
-      return rc;
-    if (hipMemsetAsync(w.counters, 0, sizeof(int) * (4 * B + pt2q_ssr_counter_ints(n)), st) != hipSuccess)
-      return PT2Q_E_HIP;
-    if (hipMemsetAsync(iters, 0, sizeof(int) * B, st) != hipSuccess) return PT2Q_E_HIP;
-    // rem0 = [0, m)
-    if ((rc = pt2q_launch_select_seq(0, 0, 0, m, nullptr, w.blk, w.rem[0], nullptr, st)) != PT2Q_OK)
-      return rc;
+    hipLaunchKernelGGL(pc_setup_group_kernel, dim3(ceil_div(m, 256), count), dim3(256), 0, st, sg, m);
+    PT2Q_LAUNCH_CHECK();
   }
-  float* part = w.ssr;
-  float* wn = part + (size_t)ceil_div(m, 128) * n;
-  float* sim = wn + n;
-  int processed = 0, r = m, cur = 0;
-  bool pre = false;  // part holds rem's w-bar partials (from the previous block's error feedback)
-  for (int k = 0; k < B; ++k) {
-    const int bs = r < b ? r : b;
-    const int nr = r - bs;
-    int* rem = w.rem[cur];
-    int* nrem = w.rem[cur ^ 1];
-    // variant M with blocks <= 128: the ATQ launch also forms S1/d (no separate launch; off
-    // the critical path of the rows, which need it only for their AGA)
-    const bool s1_in_atq = aga == PT2Q_AGA_ACT && bs <= 128;
-    StageScope ts_ssr(PT2Q_TIMER_SSR, st);
-    if (ssr) {
-      if (r > b) {
-        if ((rc = pt2q_launch_ssr_similarity(w.Wt, w.ldw, n, rem, r, part, wn, sim, st, w.counters + 4 * B,
-                                             nullptr, pre)) != PT2Q_OK)
-          return rc;
-        if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm + processed, st)) != PT2Q_OK)
-          return rc;
-      } else {
-        if ((rc = pt2q_launch_select_seq(1, 0, bs, m, rem, w.blk, nrem, perm + processed, st)) != PT2Q_OK)
-          return rc;
-      }
-    } else {
-      if ((rc = pt2q_launch_select_seq(0, processed, bs, m, nullptr, w.blk, nrem, perm + processed, st)) != PT2Q_OK)
-        return rc;
-    }
-    ts_ssr.close();
-    StageScope ts_atq(PT2Q_TIMER_ATQ, st);
-    const float* S1 = nullptr;
-    if (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_HESS) {
-      if (hess_wide(flags, bs)) {
-        if ((rc = hess_block_s1(A, lda, w.blk, bs, w, st)) != PT2Q_OK) return rc;
-      } else if (!s1_in_atq &&
-                 (rc = pt2q_launch_aga_s1(aga == PT2Q_AGA_ACT ? 1 : 2, A, lda, w.blk, bs, w.S1, w.d, st)) != PT2Q_OK) {
-        return rc;
-      }
-      S1 = w.S1;
-    }
-    if ((rc = pt2q_launch_atq_block(w.Wt, w.ldw, n, w.blk, bs, S1, w.d, max_iter,
-                                    w.alpha_t + (size_t)k * n, w.mu_t + (size_t)k * n, w.Tt, w.ldw,
-                                    nr > 0 ? w.Et : nullptr, w.ldw, iters + k, w.counters + 2 * k,
-                                    st, Hinv, ldhi, nrem, nr, w.Ck, m, w.iters_part,
-                                    s1_in_atq ? A : nullptr, lda,
-                                    s1_in_atq ? w.counters + 2 * B + 2 * k : nullptr, w.status)) != PT2Q_OK)
-      return rc;  // (also forms the EF coefficients C[k][e] when nr > 0)
-    ts_atq.close();
-    StageScope ts_ef(PT2Q_TIMER_EF, st);
-    const bool want = ssr && nr > b && ef_wbar_ok(n, w.ldw, w.Wt);  // the next block runs SSR over nrem
-    rc = nr > 0 ? pt2q_launch_ef(w.Ck, m, w.Et, w.Wt, w.ldw, m, nrem, nr, bs, st, nullptr, want ? part : nullptr, n)
-                : PT2Q_E_UNSUPPORTED;
-    if (rc != PT2Q_OK && rc != PT2Q_E_UNSUPPORTED) return rc;
-    pre = want && rc == PT2Q_OK;
-    if (nr > 0 && rc == PT2Q_E_UNSUPPORTED) {
-      GemmDesc g{};
-      g.M = nr; g.N = n; g.K = bs;
-      g.A = w.Ck; g.lda = m; g.a_layout = LAY_KMAJOR;     // (e, k) = C[k][e]
-      g.B = w.Et; g.ldb = w.ldw; g.b_layout = LAY_KMAJOR; // (k, i) = E[k][i]
-      g.in_dtype = PT2Q_F32;
-      g.C = w.Wt; g.ldc = w.ldw; g.crow = nrem;
-      g.mode = GEMM_SUB;
-      if ((rc = pt2q_launch_gemm(g, st)) != PT2Q_OK) return rc;
-    }
-    processed += bs;
-    r = nr;
-    cur ^= 1;
-  }
-  // outputs: T (n x m) from Tt (m x ldw); alpha/mu (n x B) from (B x n)
-  StageScope ts(PT2Q_TIMER_OUT, st);
-  if ((rc = pt2q_launch_transpose_i8(w.Tt, w.ldw, m, n, T, tdtype, m, st)) != PT2Q_OK) return rc;
-  if ((rc = pt2q_launch_transpose_f32(w.alpha_t, n, B, n, alpha, B, st)) != PT2Q_OK) return rc;
-  if ((rc = pt2q_launch_transpose_f32(w.mu_t, n, B, n, mu, B, st)) != PT2Q_OK) return rc;
-  return PT2Q_OK;
+  StageScope ts_atq(PT2Q_TIMER_ATQ, st);
+  return pt2q_launch_atq_rm_group(count, lin, wdtype, m, max_iter, tdtype, st);
 }
 
-// ---- grouped block loops (pt2q_quantize_blocks_group): per-linear workspace slices of one size
+// ---- the block loop of one linear (grp == nullptr, count == 1) or of a group of same-shaped
+// linears (pt2q_quantize_blocks_group: grp given, w = linear 0's slice of `count` workspace slices
+// grp->ws bytes apart, perm64 in the slice)
 
 // A linear's slice: the block-loop buffers plus its permutation (int64, written by the
 // selection launches and copied out at the end).
@@ -365,32 +260,45 @@ __global__ void group_init_kernel(int* counters, int ncnt, int* iters, int B, in
   if (t < m) rem0[t] = t;
 }
 
-int run_blocks_group(int count, const void* const* W, int wdtype, long ldw_in, int n, int m, int b,
-                     int flags, const float* const* A, long lda, const float* const* Hinv, long ldhi,
-                     int max_iter, float* const* alpha, float* const* mu, void* const* T, int tdtype,
-                     int64_t* const* perm, int* const* iters_dev, BlockWs& w, int64_t* perm64,
-                     long zs, hipStream_t st) {
+int run_blocks(int count, const void* const* W, int wdtype, long ldw_in, int n, int m, int b, int flags,
+               const float* const* A, long lda, const float* const* Hinv, long ldhi, int max_iter,
+               float* const* alpha, float* const* mu, void* const* T, int tdtype, int64_t* const* perm,
+               int* const* iters_dev, BlockWs& w, const Grp* grp, int64_t* perm64, hipStream_t st) {
   int rc;
-  const int B = ceil_div(m, b);
+  const int B = b < m ? ceil_div(m, b) : 1;
+  const long zs = grp ? grp->ws : 0;
   const bool ssr = (flags & PT2Q_FLAG_SSR) != 0;
-  const bool act = (flags & PT2Q_AGA_MASK) == PT2Q_AGA_ACT;
-  Grp g{};
-  g.ws = zs;
-  g.count = count;
-  StageScope ts0(PT2Q_TIMER_SETUP, st);
-  for (int z = 0; z < count; ++z) {
-    g.G[z] = act ? A[z] : nullptr;
-    g.Hinv[z] = Hinv[z];
-    // W (n x m) -> Wt (m x ldw, fp32) of every linear
-    if ((rc = pt2q_launch_transpose_to_f32(W[z], wdtype, ldw_in, n, m, (float*)((char*)w.Wt + z * zs), w.ldw,
-                                           st)) != PT2Q_OK)
-      return rc;
+  const int aga = flags & PT2Q_AGA_MASK;
+  // one linear: perm and iters straight into the caller's buffers; a group: into the slices
+  int64_t* pout = grp ? perm64 : perm[0];
+  int* iters = !grp && iters_dev[0] ? iters_dev[0] : w.iters;
+  if (B == 1 && m > 512 && aga != PT2Q_AGA_HESS) {
+    // Per-channel (block_size >= m, main.py:176-189 with one block; never a group, group_ok): the
+    // block is every column in ascending order -- SSR over the whole remaining set returns it in
+    // rem order, and rem is [0, m) -- so the wide ATQ reads the caller's row-major W in place (no
+    // feature-major copy, no code transpose).
+    const bool act = aga == PT2Q_AGA_ACT;
+    // S1 / d given (PT2Q_FLAG_S1_GIVEN: A = S1 then d, formed once per Gram) or formed here
+    const bool given = act && (flags & PT2Q_FLAG_S1_GIVEN) != 0;
+    if (act && !given) {
+      StageScope ts_s1(PT2Q_TIMER_ATQ, st);  // part of the ATQ stage, as the rows' launches
+      if ((rc = pt2q_launch_aga_s1(1, A[0], lda, nullptr, m, w.S1, w.d, st)) != PT2Q_OK) return rc;
+    }
+    const PcLinear lin{W[0], ldw_in, n, !act ? nullptr : given ? A[0] : w.S1, given ? A[0] + m : w.d,
+                       alpha[0], mu[0], T[0], (long)m, iters, w.counters, perm[0]};
+    return run_perchannel(1, &lin, wdtype, m, max_iter, tdtype, st);
   }
-  const int ncnt = 4 * B + pt2q_ssr_counter_ints(n);
-  hipLaunchKernelGGL(group_init_kernel, dim3(ceil_div(std::max(std::max(ncnt, B), m), 256), 1, count), dim3(256),
-                     0, st, w.counters, ncnt, w.iters, B, w.rem[0], m, zs);
-  PT2Q_LAUNCH_CHECK();
-  ts0.close();
+  {
+    StageScope ts(PT2Q_TIMER_SETUP, st);
+    for (int z = 0; z < count; ++z)  // W (n x m) -> Wt (m x ldw, fp32) of every linear
+      if ((rc = pt2q_launch_transpose_to_f32(W[z], wdtype, ldw_in, n, m, (float*)((char*)w.Wt + z * zs), w.ldw,
+                                             st)) != PT2Q_OK)
+        return rc;
+    const int ncnt = 4 * B + pt2q_ssr_counter_ints(n);
+    hipLaunchKernelGGL(group_init_kernel, dim3(ceil_div(std::max(std::max(ncnt, B), m), 256), 1, count), dim3(256),
+                       0, st, w.counters, ncnt, iters, B, w.rem[0], m, zs);
+    PT2Q_LAUNCH_CHECK();
+  }
   float* part = w.ssr;
   float* wn = part + (size_t)ceil_div(m, 128) * n;
   float* sim = wn + n;
@@ -401,46 +309,72 @@ int run_blocks_group(int count, const void* const* W, int wdtype, long ldw_in, i
     const int nr = r - bs;
     int* rem = w.rem[cur];
     int* nrem = w.rem[cur ^ 1];
+    // variant M with blocks <= 128: the ATQ launch also forms S1/d (no separate launch; off
+    // the critical path of the rows, which need it only for their AGA)
+    const bool s1_in_atq = aga == PT2Q_AGA_ACT && bs <= 128;
     StageScope ts_ssr(PT2Q_TIMER_SSR, st);
     if (ssr && r > b) {
-      if ((rc = pt2q_launch_ssr_similarity(w.Wt, w.ldw, n, rem, r, part, wn, sim, st, w.counters + 4 * B, &g,
+      if ((rc = pt2q_launch_ssr_similarity(w.Wt, w.ldw, n, rem, r, part, wn, sim, st, w.counters + 4 * B, grp,
                                            pre)) != PT2Q_OK)
         return rc;
-      if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, perm64 + processed, st, &g)) != PT2Q_OK)
+      if ((rc = pt2q_launch_ssr_topk(sim, rem, r, b, w.blk, nrem, pout + processed, st, grp)) != PT2Q_OK)
         return rc;
     } else if ((rc = pt2q_launch_select_seq(ssr ? 1 : 0, ssr ? 0 : processed, bs, m, ssr ? rem : nullptr, w.blk,
-                                            nrem, perm64 + processed, st, &g)) != PT2Q_OK) {
+                                            nrem, pout + processed, st, grp)) != PT2Q_OK) {
       return rc;
     }
     ts_ssr.close();
     StageScope ts_atq(PT2Q_TIMER_ATQ, st);
-    // variant M: S1/d of every linear's block formed inside its ATQ launch (table g.G)
-    if ((rc = pt2q_launch_atq_block(w.Wt, w.ldw, n, w.blk, bs, act ? w.S1 : nullptr, w.d, max_iter,
+    const float* S1 = nullptr;
+    if (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_HESS) {
+      // one linear only (group_ok): variant G, and variant M's blocks wider than 128 columns
+      if (hess_wide(flags, bs)) {
+        if ((rc = hess_block_s1(A[0], lda, w.blk, bs, w, st)) != PT2Q_OK) return rc;
+      } else if (!s1_in_atq && (rc = pt2q_launch_aga_s1(aga == PT2Q_AGA_ACT ? 1 : 2, A[0], lda, w.blk, bs, w.S1,
+                                                        w.d, st)) != PT2Q_OK) {
+        return rc;
+      }
+      S1 = w.S1;
+    }
+    // (a group: the Gram and the inverse Hessian of linear z from grp's tables)
+    if ((rc = pt2q_launch_atq_block(w.Wt, w.ldw, n, w.blk, bs, S1, w.d, max_iter,
                                     w.alpha_t + (size_t)k * n, w.mu_t + (size_t)k * n, w.Tt, w.ldw,
-                                    nr > 0 ? w.Et : nullptr, w.ldw, w.iters + k, w.counters + 2 * k, st,
-                                    Hinv[0], ldhi, nrem, nr, w.Ck, m, w.iters_part, act ? A[0] : nullptr, lda,
-                                    act ? w.counters + 2 * B + 2 * k : nullptr, w.status, &g)) != PT2Q_OK)
-      return rc;
+                                    nr > 0 ? w.Et : nullptr, w.ldw, iters + k, w.counters + 2 * k,
+                                    st, Hinv[0], ldhi, nrem, nr, w.Ck, m, w.iters_part,
+                                    s1_in_atq ? A[0] : nullptr, lda,
+                                    s1_in_atq ? w.counters + 2 * B + 2 * k : nullptr, w.status, grp)) != PT2Q_OK)
+      return rc;  // (also forms the EF coefficients C[k][e] when nr > 0)
     ts_atq.close();
     StageScope ts_ef(PT2Q_TIMER_EF, st);
     const bool want = ssr && nr > b && ef_wbar_ok(n, w.ldw, w.Wt);  // the next block runs SSR over nrem
-    if (nr > 0 && (rc = pt2q_launch_ef(w.Ck, m, w.Et, w.Wt, w.ldw, m, nrem, nr, bs, st, &g,
-                                       want ? part : nullptr, n)) != PT2Q_OK)
-      return rc;
-    pre = want && nr > 0;
+    rc = nr > 0 ? pt2q_launch_ef(w.Ck, m, w.Et, w.Wt, w.ldw, m, nrem, nr, bs, st, grp, want ? part : nullptr, n)
+                : PT2Q_OK;
+    pre = want && rc == PT2Q_OK;
+    if (rc == PT2Q_E_UNSUPPORTED && !grp) {  // blocks wider than the EF kernel takes: the GEMM
+      GemmDesc g{};
+      g.M = nr; g.N = n; g.K = bs;
+      g.A = w.Ck; g.lda = m; g.a_layout = LAY_KMAJOR;     // (e, k) = C[k][e]
+      g.B = w.Et; g.ldb = w.ldw; g.b_layout = LAY_KMAJOR; // (k, i) = E[k][i]
+      g.in_dtype = PT2Q_F32;
+      g.C = w.Wt; g.ldc = w.ldw; g.crow = nrem;
+      g.mode = GEMM_SUB;
+      rc = pt2q_launch_gemm(g, st);
+    }
+    if (rc != PT2Q_OK) return rc;
     processed += bs;
     r = nr;
     cur ^= 1;
   }
-  StageScope ts1(PT2Q_TIMER_OUT, st);
-  for (int z = 0; z < count; ++z) {  // outputs: T (n x m), alpha / mu (n x B), perm, iters
+  StageScope ts(PT2Q_TIMER_OUT, st);
+  for (int z = 0; z < count; ++z) {
+    // outputs: T (n x m) from Tt (m x ldw); alpha / mu (n x B) from (B x n); a group's perm, iters
     auto sl = [&](auto* p) { return (decltype(p))((char*)p + z * zs); };
     if ((rc = pt2q_launch_transpose_i8(sl(w.Tt), w.ldw, m, n, T[z], tdtype, m, st)) != PT2Q_OK) return rc;
     if ((rc = pt2q_launch_transpose_f32(sl(w.alpha_t), n, B, n, alpha[z], B, st)) != PT2Q_OK) return rc;
     if ((rc = pt2q_launch_transpose_f32(sl(w.mu_t), n, B, n, mu[z], B, st)) != PT2Q_OK) return rc;
-    if (hipMemcpyAsync(perm[z], sl(perm64), sizeof(int64_t) * m, hipMemcpyDeviceToDevice, st) != hipSuccess)
+    if (grp && hipMemcpyAsync(perm[z], sl(perm64), sizeof(int64_t) * m, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return PT2Q_E_HIP;
-    if (iters_dev && iters_dev[z] &&
+    if (grp && iters_dev && iters_dev[z] &&
         hipMemcpyAsync(iters_dev[z], sl(w.iters), sizeof(int) * B, hipMemcpyDeviceToDevice, st) != hipSuccess)
       return PT2Q_E_HIP;
   }
@@ -659,8 +593,8 @@ extern "C" int pt2q_quantize_blocks(const void* W, int wdtype, int64_t ldw, int 
   w.status = take_status(c, (hipStream_t)stream, rc);
   if (rc != PT2Q_OK) return rc;
   if (!carve_blocks(c, n, m, b, w, flags)) return PT2Q_E_WORKSPACE;
-  return run_blocks(W, wdtype, ldw, n, m, b, flags, A, lda, Hinv, ldhi, max_iter, alpha, mu, T,
-                    tdtype, perm, iters_dev, w, (hipStream_t)stream);
+  return run_blocks(1, &W, wdtype, ldw, n, m, b, flags, &A, lda, &Hinv, ldhi, max_iter, &alpha, &mu, &T,
+                    tdtype, &perm, &iters_dev, w, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" size_t pt2q_quantize_perchannel_group_workspace_bytes(int count) {
@@ -687,23 +621,13 @@ extern "C" int pt2q_quantize_perchannel_group(int count, const void* const* W, i
   int* ints = c.take<int>((size_t)count * 3);
   if (!c.ok) return PT2Q_E_WORKSPACE;
   PcLinear lin[PT2Q_PC_GROUP_MAX];
-  PcSetupGroup sg{};
   for (int z = 0; z < count; ++z) {
     const float* s1 = S1d ? S1d[z] : nullptr;
     int* it = (iters_dev && iters_dev[z]) ? iters_dev[z] : ints + 2 * count + z;
     lin[z] = PcLinear{W[z], (long)ldw, n[z], s1, s1 ? s1 + m : nullptr, alpha[z], mu[z], T[z], (long)m, it,
                       ints + 2 * z, perm[z]};
-    sg.perm[z] = perm[z];
-    sg.counters[z] = ints + 2 * z;
-    sg.iters[z] = it;
   }
-  {
-    StageScope ts(PT2Q_TIMER_SETUP, st);
-    hipLaunchKernelGGL(pc_setup_group_kernel, dim3(ceil_div(m, 256), count), dim3(256), 0, st, sg, m);
-    PT2Q_LAUNCH_CHECK();
-  }
-  StageScope ts_atq(PT2Q_TIMER_ATQ, st);
-  return pt2q_launch_atq_rm_group(count, lin, wdtype, m, max_iter, tdtype, st);
+  return run_perchannel(count, lin, wdtype, m, max_iter, tdtype, st);
 }
 
 extern "C" size_t pt2q_quantize_blocks_group_workspace_bytes(int count, int n, int m, int b, int flags) {
@@ -743,8 +667,15 @@ extern "C" int pt2q_quantize_blocks_group(int count, const void* const* W, int w
   if (!carve_blocks(s0, n, m, b, w, flags)) return PT2Q_E_WORKSPACE;
   int64_t* perm64 = s0.take<int64_t>((size_t)m);
   if (!s0.ok) return PT2Q_E_WORKSPACE;
-  return run_blocks_group(count, W, wdtype, ldw, n, m, b, flags, A, lda, Hinv, ldhi, max_iter, alpha, mu, T,
-                          tdtype, perm, iters_dev, w, perm64, (long)slice, st);
+  Grp g{};
+  g.ws = (long)slice;
+  g.count = count;
+  for (int z = 0; z < count; ++z) {
+    g.G[z] = aga == PT2Q_AGA_ACT ? A[z] : nullptr;
+    g.Hinv[z] = Hinv[z];
+  }
+  return run_blocks(count, W, wdtype, ldw, n, m, b, flags, A, lda, Hinv, ldhi, max_iter, alpha, mu, T, tdtype,
+                    perm, iters_dev, w, &g, perm64, st);
 }
 
 extern "C" int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n, int m,
@@ -798,8 +729,10 @@ extern "C" int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n
   }
   ts_inv.close();
   int f = (flags & ~PT2Q_AGA_MASK) | PT2Q_AGA_ACT;
-  return run_blocks(W, wdtype, ldw, n, m, b, f, G, m, Hinv, m, max_iter, alpha, mu, T, tdtype,
-                    perm, iters_dev, w, st);
+  const float* Gc = G;
+  const float* Hc = Hinv;
+  return run_blocks(1, &W, wdtype, ldw, n, m, b, f, &Gc, m, &Hc, m, max_iter, &alpha, &mu, &T, tdtype,
+                    &perm, &iters_dev, w, nullptr, nullptr, st);
 }
 
 extern "C" int pt2q_s1_from_gram(const float* S, int64_t lds, int b, float* S1, float* d_dev,

@@ -1245,45 +1245,14 @@ int pt2q_launch_atq_block(const float* Wt, long ldw, int n, const int* blk, int 
   });
 }
 
-// Per-channel block of the block loop (b = m > 512, one block of every column in ascending
-// order): the wide ATQ on the caller's row-major W (wdtype f32 / f16 / bf16, read as exact fp32)
-// writing T (tdtype int8 / f32, ld ldt) and alpha / mu (n) in place -- the same values, in the
-// same order, as the feature-major wide path on the transposed copy (LayRM vs LayFM: only the
-// addresses differ).  counters[0] (zero rows) and *iters are zeroed by the caller.
-int pt2q_launch_atq_wide_rm(const void* W, int wdtype, long ldw, int n, int b, const float* S1, const float* d,
-                            int max_iter, float* alpha, float* mu, void* T, int tdtype, long ldt, int* iters,
-                            int* counters, hipStream_t st) {
-  WideArgs WA{MODE_BLOCK, (const float*)W, ldw, n, b, nullptr, S1, d, max_iter, alpha, mu, T, ldt, nullptr, 0,
-              iters, counters, 0};
-  const int wgrid = ceil_div(n, 4 * WIDE_WAVES);
-  const bool pc = pt2q_atq_pc_supported(W, wdtype, ldw, b);  // codes held on-chip (atq_pc.hip)
-  auto go = [&](auto lay) {
-    typedef decltype(lay) L;
-    if (pc) {
-      const int rc = pt2q_launch_atq_pc(W, wdtype, ldw, n, b, S1, d, max_iter, alpha, mu, T, tdtype, ldt, iters,
-                                        counters, st);
-      if (rc != PT2Q_OK) return rc;
-    } else {
-      hipLaunchKernelGGL(atq_wide_block_kernel<L>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
-      PT2Q_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(atq_wide_zero_fixup_kernel<L>, dim3(wgrid), dim3(64 * WIDE_WAVES), 0, st, WA);
-    PT2Q_LAUNCH_CHECK();
-    return PT2Q_OK;
-  };
-  const bool i8 = tdtype == PT2Q_I8;
-  switch (wdtype) {
-    case PT2Q_F32: return i8 ? go(LayRM<float, int8_t>{}) : go(LayRM<float, float>{});
-    case PT2Q_F16: return i8 ? go(LayRM<_Float16, int8_t>{}) : go(LayRM<_Float16, float>{});
-    case PT2Q_BF16: return i8 ? go(LayRM<uint16_t, int8_t>{}) : go(LayRM<uint16_t, float>{});
-  }
-  return PT2Q_E_ARG;
-}
-
-// Grouped per-channel blocks (pt2q_quantize_perchannel_group): the rows of every linear in one
-// atq_pc launch when the streamed / register kernels take them all (else each linear on the wide
-// kernel), then one repair launch for the group (grid.y = linear).  The same per-row programs as
-// pt2q_launch_atq_wide_rm: the same bits.
+// Per-channel blocks of the block loop (b = m > 512, one block of every column in ascending
+// order) of up to PT2Q_PC_GROUP_MAX linears: the wide ATQ on each caller's row-major W (wdtype
+// f32 / f16 / bf16, read as exact fp32) writing T (tdtype int8 / f32, ld ldt) and alpha / mu (n)
+// in place -- the same values, in the same order, as the feature-major wide path on the
+// transposed copy (LayRM vs LayFM: only the addresses differ).  The rows of every linear go in
+// one atq_pc launch when the streamed / register kernels (atq_pc.hip) take them all (else each
+// linear on the wide kernel), then one repair launch for the group (grid.y = linear).
+// counters[0] (zero rows) and *iters of every linear are zeroed by the caller.
 int pt2q_launch_atq_rm_group(int count, const PcLinear* lin, int wdtype, int m, int max_iter, int tdtype,
                              hipStream_t st) {
   if (count <= 0 || count > PT2Q_PC_GROUP_MAX) return PT2Q_E_ARG;

@@ -545,10 +545,3 @@ int pt2q_launch_atq_pc_group(int count, const PcLinear* lin, int wdtype, int m, 
   }
   return PT2Q_E_ARG;
 }
-
-int pt2q_launch_atq_pc(const void* W, int wdtype, long ldw, int n, int m, const float* S1, const float* d,
-                       int max_iter, float* alpha, float* mu, void* T, int tdtype, long ldt, int* iters,
-                       int* counters, hipStream_t st) {
-  const PcLinear L{W, ldw, n, S1, d, alpha, mu, T, ldt, iters, counters, nullptr};
-  return pt2q_launch_atq_pc_group(1, &L, wdtype, m, max_iter, tdtype, st);
-}

@@ -26,18 +26,12 @@ inline Grp grp_or_none(const Grp* g) {
 }
 
 // ---- ATQ (atq.hip)
-// per-channel block (b = m > 512) on the caller's row-major W, outputs in place (atq.hip)
 // per-channel rows on the caller's row-major W, codes held on-chip (atq_pc.hip)
 bool pt2q_atq_pc_supported(const void* W, int wdtype, long ldw, int m);
-int pt2q_launch_atq_pc(const void* W, int wdtype, long ldw, int n, int m, const float* S1, const float* d,
-                       int max_iter, float* alpha, float* mu, void* T, int tdtype, long ldt, int* iters,
-                       int* counters, hipStream_t st);
-int pt2q_launch_atq_wide_rm(const void* W, int wdtype, long ldw, int n, int b, const float* S1, const float* d,
-                            int max_iter, float* alpha, float* mu, void* T, int tdtype, long ldt, int* iters,
-                            int* counters, hipStream_t st);
-// grouped per-channel rows: up to PT2Q_PC_GROUP_MAX linears of one width m and W dtype (row counts
-// may differ) in one launch sequence; S1 / d per linear (nullable S1: no AGA); counters (2 ints,
-// zeroed) and *iters (zeroed) per linear
+// per-channel blocks (b = m > 512) on the callers' row-major W, outputs in place: up to
+// PT2Q_PC_GROUP_MAX linears (one or more) of one width m and W dtype (row counts may differ) in
+// one launch sequence; S1 / d per linear (nullable S1: no AGA); counters (2 ints, zeroed) and
+// *iters (zeroed) per linear
 constexpr int PT2Q_PC_GROUP_MAX = 16;
 struct PcLinear {
   const void* W;
@@ -51,7 +45,7 @@ struct PcLinear {
   long ldt;
   int* iters;
   int* counters;
-  int64_t* perm;  // the setup's [0, m) (pt2q_quantize_perchannel_group), unused by the kernels
+  int64_t* perm;  // the setup's [0, m) (api.hip run_perchannel), unused by the kernels
 };
 int pt2q_launch_atq_pc_group(int count, const PcLinear* lin, int wdtype, int m, int max_iter, int tdtype,
                              hipStream_t st);

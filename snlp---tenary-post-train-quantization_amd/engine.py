@@ -37,6 +37,33 @@ class LayerOutput:
     report: Optional["LayerReport"] = None  # quantize_unit(report=True)
 
 
+def _alloc_output(n, m, B, t_dtype, dev, iters=torch.zeros) -> LayerOutput:
+    """The outputs of an n x m linear quantised in B blocks (iters: its allocator)."""
+    return LayerOutput(torch.empty((n, B), dtype=torch.float32, device=dev),
+                       torch.empty((n, B), dtype=torch.float32, device=dev),
+                       torch.empty((n, m), dtype=t_dtype, device=dev),
+                       torch.empty(m, dtype=torch.int64, device=dev),
+                       iters(B, dtype=torch.int32, device=dev))
+
+
+def _workspace(workspace, nbytes, dev):
+    """The caller's workspace, reused when large enough, else a fresh one."""
+    return workspace if workspace is not None and workspace.numel() >= nbytes else _lib.workspace(nbytes, dev)
+
+
+def _ptr_tables(*lists, outs):
+    """Pointer tables of the tensor lists, then of the outputs' fields -> (pointers, keep-alive)."""
+    fields = [[getattr(o, f) for o in outs] for f in ("alpha", "mu", "T", "perm", "iters")]
+    arrs = [_lib.ptr_array(x) for x in (*lists, *fields)]
+    return [a[0] for a in arrs], arrs
+
+
+def _finish(rc, ws, what, check):
+    _lib.check(rc, what)
+    if check:
+        _lib.check_status(ws, what)
+
+
 def gram(X: torch.Tensor, G: Optional[torch.Tensor] = None, accumulate=False,
          workspace: Optional[torch.Tensor] = None, check: bool = True) -> torch.Tensor:
     """XᵀX (main.py:128), X (N, m) or (B, L, m).
@@ -169,11 +196,7 @@ def quantize_blocks(W: torch.Tensor, A: Optional[torch.Tensor], Hinv: Optional[t
     n, m = W.shape
     dev = W.device
     B = num_blocks(m, block_size)
-    alpha = torch.empty((n, B), dtype=torch.float32, device=dev)
-    mu = torch.empty((n, B), dtype=torch.float32, device=dev)
-    T = torch.empty((n, m), dtype=t_dtype, device=dev)
-    perm = torch.empty(m, dtype=torch.int64, device=dev)
-    iters = torch.empty(B, dtype=torch.int32, device=dev)  # zeroed by the call (run_blocks)
+    out = _alloc_output(n, m, B, t_dtype, dev, iters=torch.empty)  # iters: zeroed by the call (run_blocks)
     flags = (_lib.FLAG_SSR if use_ssr else 0) | aga
     nbytes = blocks_workspace_bytes(n, m, block_size, flags)
     if s1d is not None:
@@ -183,7 +206,7 @@ def quantize_blocks(W: torch.Tensor, A: Optional[torch.Tensor], Hinv: Optional[t
         if s1d.dtype != torch.float32 or not s1d.is_contiguous() or s1d.device != dev:
             raise ValueError("quantize_blocks: s1d must be a contiguous fp32 tensor on W's device")
         A, flags = s1d, flags | _lib.FLAG_S1_GIVEN
-    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _lib.workspace(nbytes, dev)
+    ws = _workspace(workspace, nbytes, dev)
     if Hinv is None:
         if needs_inverse(m, block_size):
             raise ValueError("quantize_blocks: Hinv is required when block_size < m (error feedback)")
@@ -191,13 +214,11 @@ def quantize_blocks(W: torch.Tensor, A: Optional[torch.Tensor], Hinv: Optional[t
         Hinv = Hinv.contiguous().float()
     rc = _lib.lib().pt2q_quantize_blocks(
         _lib.ptr(W), _lib.dtype_code(W), m, n, m, int(block_size), flags,
-        _lib.ptr(A), m, _lib.ptr(Hinv), m, int(max_iter), _lib.ptr(alpha), _lib.ptr(mu), _lib.ptr(T),
-        _lib.dtype_code(T), _lib.ptr(perm), _lib.ptr(iters), _lib.ptr(ws), ws.numel(),
+        _lib.ptr(A), m, _lib.ptr(Hinv), m, int(max_iter), _lib.ptr(out.alpha), _lib.ptr(out.mu), _lib.ptr(out.T),
+        _lib.dtype_code(out.T), _lib.ptr(out.perm), _lib.ptr(out.iters), _lib.ptr(ws), ws.numel(),
         _lib.stream_of(dev))
-    _lib.check(rc, "pt2q_quantize_blocks")
-    if check:
-        _lib.check_status(ws, "pt2q_quantize_blocks")
-    return LayerOutput(alpha, mu, T, perm, iters)
+    _finish(rc, ws, "pt2q_quantize_blocks", check)
+    return out
 
 
 def s1_from_gram_batched(G: torch.Tensor, out: Optional[torch.Tensor] = None, upper_only: bool = False) -> torch.Tensor:
@@ -252,22 +273,14 @@ def quantize_blocks_group(Ws, As, Hinvs, block_size: int = 128, use_ssr: bool = 
     Hinvs = [H.contiguous().float() for H in Hinvs]
     As = [None if A is None else A.contiguous().float() for A in As] if As is not None else [None] * count
     if outs is None:
-        outs = [LayerOutput(torch.empty((n, B), dtype=torch.float32, device=dev),
-                            torch.empty((n, B), dtype=torch.float32, device=dev),
-                            torch.empty((n, m), dtype=t_dtype, device=dev),
-                            torch.empty(m, dtype=torch.int64, device=dev),
-                            torch.zeros(B, dtype=torch.int32, device=dev)) for _ in range(count)]
+        outs = [_alloc_output(n, m, B, t_dtype, dev) for _ in range(count)]
     nbytes = _lib.lib().pt2q_quantize_blocks_group_workspace_bytes(count, n, m, int(block_size), flags)
-    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _lib.workspace(nbytes, dev)
-    arrs = [_lib.ptr_array(x) for x in (Ws, As, Hinvs, [o.alpha for o in outs], [o.mu for o in outs],
-                                        [o.T for o in outs], [o.perm for o in outs], [o.iters for o in outs])]
-    p = [a[0] for a in arrs]
+    ws = _workspace(workspace, nbytes, dev)
+    p, keep = _ptr_tables(Ws, As, Hinvs, outs=outs)
     rc = _lib.lib().pt2q_quantize_blocks_group(
         count, p[0], _lib.dtype_code(Ws[0]), m, n, m, int(block_size), flags, p[1], m, p[2], m, int(max_iter),
         p[3], p[4], p[5], _lib.dtype_code(outs[0].T), p[6], p[7], _lib.ptr(ws), ws.numel(), _lib.stream_of(dev))
-    _lib.check(rc, "pt2q_quantize_blocks_group")
-    if check:
-        _lib.check_status(ws, "pt2q_quantize_blocks_group")
+    _finish(rc, ws, "pt2q_quantize_blocks_group", check)
     return outs
 
 
@@ -302,25 +315,16 @@ def quantize_perchannel_group(Ws, s1ds=None, max_iter: int = 100, t_dtype=torch.
                                   or t.device != dev):
                 raise ValueError("quantize_perchannel_group: s1d must be m + 1 contiguous fp32 on W's device")
     if outs is None:
-        outs = [LayerOutput(torch.empty((W.shape[0], 1), dtype=torch.float32, device=dev),
-                            torch.empty((W.shape[0], 1), dtype=torch.float32, device=dev),
-                            torch.empty((W.shape[0], m), dtype=t_dtype, device=dev),
-                            torch.empty(m, dtype=torch.int64, device=dev),
-                            torch.zeros(1, dtype=torch.int32, device=dev)) for W in Ws]
+        outs = [_alloc_output(W.shape[0], m, 1, t_dtype, dev) for W in Ws]
     nbytes = _lib.lib().pt2q_quantize_perchannel_group_workspace_bytes(count)
-    ws = workspace if workspace is not None and workspace.numel() >= nbytes else _lib.workspace(nbytes, dev)
+    ws = _workspace(workspace, nbytes, dev)
     import ctypes
     ns = (ctypes.c_int * count)(*[W.shape[0] for W in Ws])
-    arrs = [_lib.ptr_array(x) for x in (Ws, [None] * count if s1ds is None else s1ds, [o.alpha for o in outs],
-                                        [o.mu for o in outs], [o.T for o in outs], [o.perm for o in outs],
-                                        [o.iters for o in outs])]
-    p = [a[0] for a in arrs]
+    p, keep = _ptr_tables(Ws, [None] * count if s1ds is None else s1ds, outs=outs)
     rc = _lib.lib().pt2q_quantize_perchannel_group(
         count, p[0], _lib.dtype_code(Ws[0]), m, ctypes.cast(ns, ctypes.c_void_p), m, p[1], int(max_iter),
         p[2], p[3], p[4], _lib.dtype_code(outs[0].T), p[5], p[6], _lib.ptr(ws), ws.numel(), _lib.stream_of(dev))
-    _lib.check(rc, "pt2q_quantize_perchannel_group")
-    if check:
-        _lib.check_status(ws, "pt2q_quantize_perchannel_group")
+    _finish(rc, ws, "pt2q_quantize_perchannel_group", check)
     return outs
 
 

@@ -631,13 +631,15 @@ def test_reference_call_shapes_with_cpu_tensors(pt2q):
                                              (512, 384, 2, False, torch.float32), (1024, 1024, 16, True, torch.float16),
                                              (4096, 4096, 3, True, torch.float16), (1000, 512, 3, True, torch.float16),
                                              (11008, 4096, 3, True, torch.float16),
-                                             (4096, 11008, 2, True, torch.float16)])
+                                             (4096, 11008, 2, True, torch.float16),
+                                             (64, 260, 1, True, torch.float32)])
 def test_blocks_group_equals_per_linear(pt2q, n, m, count, ssr, dt):
     """pt2q_quantize_blocks_group (one launch per block step for all linears, grid.z = linear)
     == quantize_blocks on each linear alone, bit for bit: every linear has its own W, raw Gram
     and H^-1 (and some share them, as q/k/v do); ragged m, fp16 weights, sequential blocks, a
     full group of 16, and the 7B step's MLP shapes as the bench groups them (gate/up 11008 x
-    4096: n > 4096 takes the split similarity kernel ssr_sim_split_kernel; down 4096 x 11008)."""
+    4096: n > 4096 takes the split similarity kernel ssr_sim_split_kernel; down 4096 x 11008), and
+    a group of one linear with a ragged last block (260 = 128 + 128 + 4 columns)."""
     Ws, Gs, Hs = [], [], []
     for z in range(count):
         X = pt2q.fill_synthetic((2 * m + 64 * z, m), 300 + 7 * z, outliers=True, device="cuda").half()
