@@ -210,7 +210,7 @@ __global__ __launch_bounds__(256) void chol_panel_trtri_kernel(float* U, long ld
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-#include "chol_lane.inc"  // lane_stream_panel / lane_stream_inverse (tools/gen_chol_lane.py)
+#include "chol_lane.hpp"  // pt2q_lane::stream: the step stream of the panel solve / in-block inverse
 
 PT2Q_DEV void lane_stage_block(float (*Ds)[NB], const float* U, long ld, int p0) {
   const float* D = U + (long)p0 * ld + p0;
@@ -235,7 +235,7 @@ PT2Q_DEV void lane_panel(float* U, long ld, int p0, int m, int t, float (*Ds)[NB
   for (int r = 0; r < NB / 2; ++r) xp[r] = f32x2{col[(long)(2 * r) * ld], col[(long)(2 * r + 1) * ld]};
   lane_stage_block(Ds, U, ld, p0);  // (the chains' loads in flight meanwhile)
   __syncthreads();
-  lane_stream_panel(xp, lds_addr(&Ds[0][0]));
+  pt2q_lane::stream<false>(xp, lds_addr(&Ds[0][0]), 0);
   if (!valid) return;
 #pragma unroll
   for (int r = 0; r < NB / 2; ++r) {
@@ -257,7 +257,7 @@ PT2Q_DEV void lane_inverse(const float* U, float* Ui, long ld, int p0, int k, fl
   lane_stage_block(Ds, U, ld, p0);
   __syncthreads();
   const int kl = k - p0;  // the row's own diagonal step (none for k < p0)
-  lane_stream_inverse(xp, lds_addr(&Ds[0][0]), kl);
+  pt2q_lane::stream<true>(xp, lds_addr(&Ds[0][0]), kl);
   if (k >= p0 + NB) return;
   const int jb = kl > 0 ? kl : 0;
 #pragma unroll

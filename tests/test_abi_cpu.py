@@ -211,21 +211,37 @@ def test_gram_order_tables_cover_every_tile_once():
     assert len(tab) == offs[-1] + Ts[-1] * (Ts[-1] + 1) // 2
 
 
-def test_chol_lane_stream_keeps_chain_order():
-    """csrc/chol_lane.inc (tools/gen_chol_lane.py): the committed stream is the generator's output,
-    and replaying its items symbolically, every chain receives the terms of rows 0, 1, 2, ... in
-    ascending order and row R's value is used only once chain R has all its terms and its
-    division -- the PT2Q chain order, so the one-lane kernel's bits are the oracle's."""
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("gen_chol_lane", os.path.join(ROOT, "tools", "gen_chol_lane.py"))
-    gen = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(gen)
-    src = open(gen.OUT).read()
-    assert gen.gen(False) in src and gen.gen(True) in src
-    NB = gen.NB
+def test_chol_lane_stream_keeps_chain_order(tmp_path):
+    """csrc/chol_lane.hpp: a host program prints the constexpr schedule the one-lane kernel is
+    expanded from (R c diag offset slot wait per item).  Replaying its items symbolically, every
+    chain receives the terms of rows 0, 1, 2, ... in ascending order and row R's value is used only
+    once chain R has all its terms and its division -- the PT2Q chain order, so the one-lane
+    kernel's bits are the oracle's -- and every item's LDS offset, ring slot and lgkmcnt wait are
+    the ones its place in the stream demands."""
+    import shutil
+    import subprocess
+    csrc = os.path.join(ROOT, "snlp---tenary-post-train-quantization_amd", "csrc")
+    prog = tmp_path / "lane_items.cpp"
+    prog.write_text("""#include <cstdio>
+#include "chol_lane.hpp"
+int main() {
+  using namespace pt2q_lane;
+  for (int i = 0; i < N; ++i)
+    std::printf("%d %d %d %d %d %d\\n", item(i).R, item(i).c, (int)item(i).diag, offset(i), slot(i), wait(i));
+}
+""")
+    # hipcc (the Makefile's, as a plain host compiler) is present wherever the library was built
+    found = [shutil.which(c) for c in (os.environ.get("CXX"), "c++", "hipcc", "/opt/rocm/bin/hipcc") if c]
+    cxx = next(c for c in found if c)
+    exe = str(tmp_path / "lane_items")
+    subprocess.check_call([cxx, "-std=c++17", "-I", csrc, "-x", "c++", str(prog), "-o", exe])
+    items = [tuple(map(int, ln.split())) for ln in subprocess.check_output([exe], text=True).splitlines()]
+    NB, PRE, n = 64, 10, len(items)
+    assert n == sum(NB // 4 - R // 4 for R in range(NB))
+    assert len({(R, c) for R, c, *_ in items}) == n and all(R // 4 <= c < NB // 4 for R, c, *_ in items)
     terms = [[] for _ in range(NB)]  # rows applied to each chain, in order
     final = set()
-    for R, c, diag in gen.stream():
+    for i, (R, c, diag, off, slot, wait) in enumerate(items):
         if diag:
             assert terms[R] == list(range(R)), R  # chain R complete before its division
             final.add(R)
@@ -233,5 +249,8 @@ def test_chol_lane_stream_keeps_chain_order():
         for j in range(4 * c, 4 * c + 4):
             if j > R:
                 terms[j].append(R)
+        assert off == (R * NB + 4 * c) * 4 and slot == i % PRE, i
+        # reads come back in order: the wait leaves outstanding exactly the reads issued after item i
+        assert wait == min(n, i + PRE) - i - 1, i
     assert all(terms[j] == list(range(j)) for j in range(NB))
     assert final == set(range(NB))
