@@ -171,30 +171,6 @@ size_t blocks_bytes(int n, int m, int b, int flags = 0) {  // a dry run of carve
   return c.used;
 }
 
-// hb[t][j] = A[blk[t]][blk[j]] (bs x bs, ld bs): variant G's X_block = H[blk][:, blk] (gptq.py:147)
-__global__ void gather_block_kernel(const float* A, long lda, const int* blk, int bs, float* hb) {
-  const int j = blockIdx.x * blockDim.x + threadIdx.x, t = blockIdx.y;
-  if (j < bs) hb[(long)t * bs + j] = A[(long)blk[t] * lda + blk[j]];
-}
-
-// S1 = (H_bbᵀH_bb)·1, d = 1ᵀS1 for blocks > 128 columns (quantizer.py:202-218 with X = H_bb):
-// S on the f32 MFMA GEMM (t-ascending fmaf chains, as aga_s1_kernel's src 2), then the row sums
-// in l order and d in j order (pt2q_launch_aga_s1 src 1 on S itself).
-int hess_block_s1(const float* A, long lda, const int* blk, int bs, BlockWs& w, hipStream_t st) {
-  hipLaunchKernelGGL(gather_block_kernel, dim3(ceil_div(bs, 256), bs), dim3(256), 0, st, A, lda, blk, bs, w.hb);
-  PT2Q_LAUNCH_CHECK();
-  GemmDesc g{};
-  g.M = bs; g.N = bs; g.K = bs;
-  g.A = w.hb; g.lda = bs; g.a_layout = LAY_KMAJOR;  // (j, t) = hb[t][j]
-  g.B = w.hb; g.ldb = bs; g.b_layout = LAY_KMAJOR;  // (t, l) = hb[t][l]
-  g.in_dtype = PT2Q_F32;
-  g.C = w.hS; g.ldc = bs;
-  g.mode = GEMM_STORE;
-  int rc = pt2q_launch_gemm(g, st);
-  if (rc != PT2Q_OK) return rc;
-  return pt2q_launch_aga_s1(1, w.hS, bs, nullptr, bs, w.S1, w.d, st);
-}
-
 // per-channel setup in one launch, linear z = blockIdx.y: perm = [0, m) (the block is every column
 // in ascending order), the wide ATQ's counters (2 ints) and the iteration count zeroed -- instead
 // of two memsets and a select_seq launch per linear
@@ -282,7 +258,7 @@ int run_blocks(int count, const void* const* W, int wdtype, long ldw_in, int n, 
     const bool given = act && (flags & PT2Q_FLAG_S1_GIVEN) != 0;
     if (act && !given) {
       StageScope ts_s1(PT2Q_TIMER_ATQ, st);  // part of the ATQ stage, as the rows' launches
-      if ((rc = pt2q_launch_aga_s1(1, A[0], lda, nullptr, m, w.S1, w.d, st)) != PT2Q_OK) return rc;
+      if ((rc = pt2q_launch_s1(A[0], lda, nullptr, m, w.S1, w.d, st)) != PT2Q_OK) return rc;
     }
     const PcLinear lin{W[0], ldw_in, n, !act ? nullptr : given ? A[0] : w.S1, given ? A[0] + m : w.d,
                        alpha[0], mu[0], T[0], (long)m, iters, w.counters, perm[0]};
@@ -328,12 +304,13 @@ int run_blocks(int count, const void* const* W, int wdtype, long ldw_in, int n, 
     const float* S1 = nullptr;
     if (aga == PT2Q_AGA_ACT || aga == PT2Q_AGA_HESS) {
       // one linear only (group_ok): variant G, and variant M's blocks wider than 128 columns
-      if (hess_wide(flags, bs)) {
-        if ((rc = hess_block_s1(A[0], lda, w.blk, bs, w, st)) != PT2Q_OK) return rc;
-      } else if (!s1_in_atq && (rc = pt2q_launch_aga_s1(aga == PT2Q_AGA_ACT ? 1 : 2, A[0], lda, w.blk, bs, w.S1,
-                                                        w.d, st)) != PT2Q_OK) {
-        return rc;
-      }
+      if (hess_wide(flags, bs))
+        rc = pt2q_launch_s1_hess_wide(A[0], lda, w.blk, bs, w.hb, w.hS, w.S1, w.d, st);
+      else if (aga == PT2Q_AGA_HESS)
+        rc = pt2q_launch_s1_hess_block(A[0], lda, w.blk, bs, w.S1, w.d, st);
+      else
+        rc = s1_in_atq ? PT2Q_OK : pt2q_launch_s1(A[0], lda, w.blk, bs, w.S1, w.d, st);
+      if (rc != PT2Q_OK) return rc;
       S1 = w.S1;
     }
     // (a group: the Gram and the inverse Hessian of linear z from grp's tables)
@@ -738,7 +715,7 @@ extern "C" int pt2q_quantize_layer(const void* W, int wdtype, int64_t ldw, int n
 extern "C" int pt2q_s1_from_gram(const float* S, int64_t lds, int b, float* S1, float* d_dev,
                                  void* stream) {
   if (!S || !S1 || !d_dev || b <= 0 || lds < b) return PT2Q_E_ARG;
-  return pt2q_launch_aga_s1(1, S, lds, nullptr, b, S1, d_dev, (hipStream_t)stream);
+  return pt2q_launch_s1(S, lds, nullptr, b, S1, d_dev, (hipStream_t)stream);
 }
 
 extern "C" int pt2q_s1_from_gram_batched(const float* S, int64_t lds, int m, int batch, int64_t item_stride,
@@ -746,7 +723,7 @@ extern "C" int pt2q_s1_from_gram_batched(const float* S, int64_t lds, int m, int
   if (!S || !S1d || m <= 0 || batch < 0 || lds < m || (batch > 1 && item_stride < lds * m)) return PT2Q_E_ARG;
   if (batch == 0) return PT2Q_OK;
   StageScope ts(PT2Q_TIMER_ATQ, (hipStream_t)stream);  // the AGA's S1 / d (quantizer.py:215-218)
-  return pt2q_launch_s1_batched(S, lds, m, batch, item_stride, S1d, (hipStream_t)stream);
+  return pt2q_launch_s1(S, lds, nullptr, m, S1d, S1d + m, (hipStream_t)stream, batch, item_stride, m + 1, S1_GRAMS);
 }
 
 extern "C" int pt2q_s1_from_upper_batched(const float* S, int64_t lds, int m, int batch, int64_t item_stride,
@@ -754,7 +731,8 @@ extern "C" int pt2q_s1_from_upper_batched(const float* S, int64_t lds, int m, in
   if (!S || !S1d || m <= 0 || batch < 0 || lds < m || (batch > 1 && item_stride < lds * m)) return PT2Q_E_ARG;
   if (batch == 0) return PT2Q_OK;
   StageScope ts(PT2Q_TIMER_ATQ, (hipStream_t)stream);
-  return pt2q_launch_s1_batched(S, lds, m, batch, item_stride, S1d, (hipStream_t)stream, true);
+  return pt2q_launch_s1(S, lds, nullptr, m, S1d, S1d + m, (hipStream_t)stream, batch, item_stride, m + 1,
+                        S1_UPPER_GRAMS);
 }
 
 extern "C" int pt2q_ssr_select(const float* W, int64_t ldw, int n, int m, const int64_t* rem, int r,
@@ -839,7 +817,7 @@ extern "C" size_t pt2q_ssr_static_order_workspace_bytes(int m) {
   Carve c{nullptr, 0};
   c.dry = true;
   c.take<int>(PT2Q_STATUS_BYTES / sizeof(int));
-  c.take<float>((size_t)m + 1);  // row sums, then their total (pt2q_launch_s1_batched's layout)
+  c.take<float>((size_t)m + 1);  // row sums, then their total (pt2q_s1_from_gram_batched's layout)
   return c.used;
 }
 
@@ -855,7 +833,7 @@ extern "C" int pt2q_ssr_static_order(const float* S, int64_t lds, int m, int64_t
   if (rc != PT2Q_OK) return rc;
   float* S1d = c.take<float>((size_t)m + 1);
   if (!c.ok) return PT2Q_E_WORKSPACE;
-  if ((rc = pt2q_launch_s1_batched(S, lds, m, 1, 0, S1d, st)) != PT2Q_OK) return rc;
+  if ((rc = pt2q_launch_s1(S, lds, nullptr, m, S1d, S1d + m, st, 1, 0, 0, S1_GRAMS)) != PT2Q_OK) return rc;
   return pt2q_launch_greedy_order(S, lds, m, S1d, perm, inv_perm, st);
 }
 

@@ -577,25 +577,11 @@ constexpr int atq_rg() { return NS == 8 ? (OCC > 0 ? 2 : 4) : 1; }
 // Iteration count of a block: one store per wave (iters_part), reduced by the post / fixup
 // launch -- not one atomic per wave on a single word (1024 atomics serialise at the memory side
 // and hold the kernel's end for ~10 us).
-// S1[j] = l-ascending sum of G[blk_j][blk_l], d = j-ascending sum of S1 (the s1_block order):
-// 8 rows j per workgroup gathered into LDS, one lane sums each; the last S1 workgroup forms d
-// and raises the flag.  Write-through stores drained before the counter / flag, sc1 loads.
+// S1[j] = l-ascending sum of G[blk_j][blk_l], d = j-ascending sum of S1 (s1_chain, the s1.hip
+// order): 8 rows j per workgroup gathered into LDS, one lane sums each; the last S1 workgroup forms
+// d and raises the flag.  Write-through stores drained before the counter / flag, sc1 loads.
 // (Measured slower: rows forming d themselves with no last-workgroup stage; one workgroup for
 // all of S1 -- its per-lane serial sums take longer than the hand-off they save.)
-PT2Q_DEV float s1_serial_sum(const float* v, int b) {  // ((v0 + v1) + v2) ..., loads batched
-  float s = 0.0f;
-  int q = 0;
-  for (; q + 8 <= b; q += 8) {
-    float t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = v[q + u];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) s = s + t[u];
-  }
-  for (; q < b; ++q) s = s + v[q];
-  return s;
-}
-
 PT2Q_DEV void atq_s1_part(const BlockArgs& A, int x) {
   __shared__ float gb[8][129];
   __shared__ int last;
@@ -611,7 +597,7 @@ PT2Q_DEV void atq_s1_part(const BlockArgs& A, int x) {
   }
   __syncthreads();
   if (ln == 0 && j < A.b)
-    __hip_atomic_store(&A.S1w[j], s1_serial_sum(gb[jj], A.b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&A.S1w[j], s1_chain(gb[jj], A.b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
   if (tid == 0) last = atomicAdd(&A.s1sync[1], 1) == A.nS1 - 1;
@@ -620,7 +606,7 @@ PT2Q_DEV void atq_s1_part(const BlockArgs& A, int x) {
   if (tid < A.b) gb[0][tid] = __hip_atomic_load(&A.S1w[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   __syncthreads();
   if (tid == 0) {
-    __hip_atomic_store(A.dw, s1_serial_sum(gb[0], A.b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(A.dw, s1_chain(gb[0], A.b), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __hip_atomic_store(&A.s1sync[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }

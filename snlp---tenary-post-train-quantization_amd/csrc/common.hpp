@@ -110,6 +110,22 @@ PT2Q_DEV float block_sumn_lds(const float* v, long n, long stride, float* lds, f
   return *out_slot;
 }
 
+// The sequential chain ((s + v0) + v1) + ... over a contiguous array: the order of the AGA's S1[j]
+// (over l) and d (over j), DESIGN.md §3 (s1.hip, atq.hip).  Loads in batches of eight, then eight
+// dependent adds, so the chain waits on memory once per batch; a scalar tail.
+PT2Q_DEV float s1_chain(const float* v, int n, float s = 0.0f) {
+  int q = 0;
+  for (; q + 8 <= n; q += 8) {
+    float t[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) t[u] = v[q + u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s = s + t[u];
+  }
+  for (; q < n; ++q) s = s + v[q];
+  return s;
+}
+
 constexpr int SUMN_LDS_MAX = 12288;  // floats staged in LDS by block_sumn_lds users (48 KiB)
 
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }

@@ -75,13 +75,24 @@ int pt2q_launch_ssr_topk(const float* sim, const int* rem, int r, int b, int* bl
                          int64_t* perm_out, hipStream_t st, const Grp* grp = nullptr);
 int pt2q_launch_select_seq(int mode, int p0, int bs, int m, const int* rem, int* blk,
                            int* newrem, int64_t* perm_out, hipStream_t st, const Grp* grp = nullptr);
-int pt2q_launch_s1_batched(const float* G, long ldg, int m, int batch, long sG, float* S1d, hipStream_t st,
-                           bool upper = false);
-int pt2q_launch_aga_s1(int src, const float* A, long lda, const int* blk, int b, float* S1,
-                       float* d, hipStream_t st);
 int pt2q_launch_ef_coeffs(const float* Hinv, long ldh, const int* blk, int bs, const int* rem,
                           int nr, float* C, long ldc, hipStream_t st);
 size_t pt2q_ssr_scratch_floats(int n, int m);
+
+// ---- the AGA's S1 = S·1, d = 1ᵀS1 (s1.hip)
+// S[j][l] = A[blk_j][blk_l] (blk nullable: the leading b x b) of `batch` items, item z at A + z * sA,
+// its S1 / d at S1 / d + z * sS.  S1_BLOCK: one block or Gram, any base / ld; S1_GRAMS: whole Grams
+// (no blk), the LDS-DMA kernel where their alignment allows; S1_UPPER_GRAMS: whole Grams of which
+// only the upper triangle is read (E_UNSUPPORTED unless b > 512 and 16-byte rows).
+enum S1Kind { S1_BLOCK = 0, S1_GRAMS = 1, S1_UPPER_GRAMS = 2 };
+int pt2q_launch_s1(const float* A, long lda, const int* blk, int b, float* S1, float* d, hipStream_t st,
+                   int batch = 1, long sA = 0, long sS = 0, int kind = S1_BLOCK);
+// variant G (S = H_bbᵀH_bb, H_bb = A[blk][:, blk]): b <= 128 in one workgroup's LDS; wider blocks
+// through hb, hS (b x b floats each) and the f32 GEMM
+int pt2q_launch_s1_hess_block(const float* A, long lda, const int* blk, int b, float* S1, float* d,
+                              hipStream_t st);
+int pt2q_launch_s1_hess_wide(const float* A, long lda, const int* blk, int bs, float* hb, float* hS, float* S1,
+                             float* d, hipStream_t st);
 
 // ---- static reorder (reorder_static.hip)
 // nrm[j] = clamp(sqrt(fmaf chain of column j), 1e-8) and Wn = W / nrm (fp32, ld ldn >= m)

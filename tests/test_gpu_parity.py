@@ -517,6 +517,7 @@ def test_layer_not_spd_pinv_fallback(pt2q):
     (640, 1000, 700, True, 256),     # ragged m, wider blocks
     (1000, 640, 700, True, 128),     # n % 16 != 0: the block ATQ's per-element form (no 16-byte stage)
     (1008, 520, 600, True, 128),     # n % 16 == 0 with a ragged last block (16-byte stage, then b = 8)
+    (48, 1100, 600, True, 520),      # blocks of 520, 520, 60: s1_rows_kernel through SSR block indices
 ])
 def test_layer_m_bitexact_larger(pt2q, n, m, N, ssr, bs):
     W = synth.weights(1000 + n, n, m)
@@ -556,7 +557,7 @@ def test_layer_headline_shape_bitexact(pt2q):
                                           (200, 700, 800, 700, False)])
 def test_gptq_wide_blocks_vs_oracle(pt2q, n, m, N, bs, ssr):
     """Variant G with blocks wider than 128 columns: S = H_bbᵀH_bb on the f32 MFMA
-    GEMM, S1 / d in the aga_s1 order; bit-exact vs the oracle's s1_from_hess_block."""
+    GEMM, S1 / d in the s1_chain order; bit-exact vs the oracle's s1_from_hess_block."""
     W = synth.weights(600 + n, n, m)
     X = synth.activations(601 + m, N, m, outliers=False)
     lin = torch.nn.Linear(m, n, bias=False).to(DEV)

@@ -428,14 +428,14 @@ def _s1_ref(m, z):
     (516, 4, 8, 1),    # s1_rows_kernel (4-byte aligned base)
     (518, 4, 6, 0),    # s1_rows_kernel (m % 4)
     (300, 4, 8, 0), (300, 1, 3, 1),    # s1_row_wg_kernel
-    (100, 4, 8, 0), (100, 1, 3, 1)])   # the per-item loop of s1_fused_kernel
+    (100, 4, 8, 0), (100, 1, 3, 1)])   # s1_fused_kernel
 def test_s1_from_gram(pt2q, m, dl, ds, lead):
     """pt2q_s1_from_gram_batched on two Grams with lds = m + dl and item_stride = lds m + ds (the
     gap between the items is NaN), then pt2q_s1_from_gram on item 1 alone.  Batched paths
-    (pt2q_launch_s1_batched) as annotated on the cases: m > 512 takes s1_ring_kernel only with
-    m, lds, item_stride multiples of 4 and a 16-byte base, else s1_rows_kernel (grid.y = item);
-    128 < m <= 512: s1_row_wg_kernel; m <= 128: pt2q_launch_aga_s1 per item.  The single entry
-    (pt2q_launch_aga_s1): s1_rows_kernel / s1_row_wg_kernel / s1_fused_kernel by m alone."""
+    (pt2q_launch_s1, S1_GRAMS; grid.y = item) as annotated on the cases: m > 512 takes
+    s1_ring_kernel only with m, lds, item_stride multiples of 4 and a 16-byte base, else
+    s1_rows_kernel; 128 < m <= 512: s1_row_wg_kernel; m <= 128: s1_fused_kernel.  The single entry
+    (S1_BLOCK): s1_rows_kernel / s1_row_wg_kernel / s1_fused_kernel by m alone."""
     L, lib, st = env(pt2q)
     lds = m + dl
     istride = lds * m + ds
@@ -709,7 +709,7 @@ def test_quantize_blocks(pt2q, dt, ldw, lda, ldhi, lead):
 @pytest.mark.parametrize("ldw,lda,ldhi,lead", [(304, 308, 312, 0), (301, 303, 305, 0), (304, 308, 312, 1)])
 def test_quantize_blocks_variant_g(pt2q, ldw, lda, ldhi, lead):
     """Variant G (PT2Q_AGA_HESS), n = 64, m = 300, b = 100: A is the damped Hessian, read through
-    lda by aga_s1_kernel (src 2: gathers H[blk][blk] into LDS by scalar loads); Hinv through ldhi
+    lda by s1_hess_block_kernel (gathers H[blk][blk] into LDS by scalar loads); Hinv through ldhi
     by the EF coefficient workgroups of atq_block_kernel; W through ldw by transpose_kernel."""
     L, lib, st = env(pt2q)
     n, m, b = 64, 300, 100
@@ -751,7 +751,7 @@ def test_quantize_blocks_per_channel(pt2q, given, ldw, lda, lead, olead):
     """Per-channel (b = m = 520 > 512), n = 70, bf16 W read in place through ldw, Hinv = NULL.
     ldw = 528 (1056-byte rows, 16-byte base): the atq_pc row kernels (pt2q_atq_pc_supported);
     ldw = 523 or lead = 1: atq_wide_block_kernel<LayRM<uint16_t, int8_t>>.  Without
-    PT2Q_FLAG_S1_GIVEN, A is the raw Gram read through lda by s1_rows_kernel (pt2q_launch_aga_s1,
+    PT2Q_FLAG_S1_GIVEN, A is the raw Gram read through lda by s1_rows_kernel (pt2q_launch_s1,
     m > 512); with it, A is S1 then d (m + 1 floats).  olead = 1: the atq_pc kernels writing
     alpha, mu and T (ld m) at bases offset by one element."""
     L, lib, st = env(pt2q)

@@ -1,6 +1,9 @@
 """PMC workloads (dev tool):
 python tools/kern_workloads.py {inverse M BATCH | group N M COUNT | grams N M COUNT | pc N M COUNT | pcg M COUNT} [reps]
+python tools/kern_workloads.py s1 M BATCH [upper] [reps]
 inverse: engine.hessian_inverse_batched on BATCH synthetic Grams of order M (N = 262144 scale);
+s1:      engine.s1_from_gram_batched on BATCH copies of one synthetic 16-bit Gram of order M
+         (upper: strictly lower triangles blanked with NaN, the upper-only kernel);
 group:   pt2q_quantize_blocks_group of COUNT fp16 N x M linears (SSR, variant M);
 pc:      per-channel block loops (block_size = M, config C5) of COUNT bf16 N x M linears;
 grams:   engine.gram_batched over COUNT Grams of DISTINCT (env, default 4) resident fp16 N x M
@@ -13,7 +16,20 @@ import pt2q_loader
 pt2q = pt2q_loader.load()
 kind = sys.argv[1]
 reps = int(sys.argv[5]) if len(sys.argv) > 5 and sys.argv[1] != "pcg" else (int(sys.argv[4]) if sys.argv[1] == "pcg" and len(sys.argv) > 4 else 3)
-if kind == "inverse":
+if kind == "s1":
+    m, batch = int(sys.argv[2]), int(sys.argv[3])
+    rest = sys.argv[4:]
+    upper = rest[:1] == ["upper"]
+    reps = int(rest[upper]) if len(rest) > upper else 3
+    X = pt2q.fill_synthetic((4096, m), 78, outliers=True).bfloat16()
+    G = pt2q.gram(X).expand(batch, m, m).contiguous()
+    if upper:
+        G.masked_fill_(torch.tril(torch.ones(m, m, dtype=torch.bool, device=G.device), -1), float("nan"))
+    for _ in range(reps):
+        S1d = pt2q.engine.s1_from_gram_batched(G, upper_only=upper)
+    torch.cuda.synchronize()
+    print("s1 done", float(S1d[0, m]))
+elif kind == "inverse":
     m, batch = int(sys.argv[2]), int(sys.argv[3])
     X = pt2q.fill_synthetic((4 * m, m), 77, outliers=True).half()
     G1 = pt2q.gram(X)
