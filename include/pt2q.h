@@ -395,6 +395,24 @@ int pt2q_ternary_decode(const void* x, int xdtype, int tokens, int64_t ldx, int 
                         const float* mu, int B, int bs, const float* bias, void* y, int ydtype,
                         int64_t ldy, void* stream);
 
+/* The same layer (model.py:75-95) for 2 .. pt2q_ternary_skinny_max_tokens() (64) tokens -- batched
+ * decode, speculative decoding, short prompts -- on the 16x16x32 MFMA with x staged through LDS and
+ * the K-split partial sums reduced inside the GEMM launch (csrc/ternary_skinny.hip): two launches,
+ * no synchronisation, capturable.  Argument list, argument rules and status codes are those of
+ * pt2q_ternary_linear, with a workspace of pt2q_ternary_skinny_workspace_bytes(tokens, n, m)
+ * bytes (0 for arguments the call would refuse); in addition more tokens than the cap, codes not
+ * 8-byte aligned or a workspace not 256-byte aligned return PT2Q_E_UNSUPPORTED.  Every check runs
+ * before anything is launched.  Nothing is read from what an earlier call left in the workspace.
+ * The partial sums are added in a fixed order, ((p0 + p1) + ...) + bias, so the result is
+ * identical run to run; it differs from pt2q_ternary_linear's in the last bits (another MFMA,
+ * another split).  1 token is served too, but pt2q_ternary_decode is the kernel for it. */
+int pt2q_ternary_skinny_max_tokens(void);
+size_t pt2q_ternary_skinny_workspace_bytes(int tokens, int n, int m);
+int pt2q_ternary_skinny(const void* x, int xdtype, int tokens, int64_t ldx, int n, int m,
+                        const uint8_t* codes, const int* gather, const float* alpha,
+                        const float* mu, int B, int bs, const float* bias, void* y, int ydtype,
+                        int64_t ldy, void* workspace, size_t workspace_bytes, void* stream);
+
 /* count (1 .. PT2Q_DECODE_GROUP_MAX) packed ternary linears that read the same x (tokens x m,
  * 1 .. 8 tokens), in ONE launch: no workspace, no allocation, no synchronisation, capturable.
  * The members share m, xdtype and bs; n, codes, gather, alpha, mu, B, bias, y and ldy are HOST

@@ -5,7 +5,9 @@ Buffers and their state_dict names are the reference's (T int8, alpha, mu, perm,
 so checkpoints move between the two.  The forward pass is the libpt2q kernel
 pt2q_ternary_linear (csrc/ternary_linear.hip): 2-bit packed codes dequantised in registers into
 f16/bf16 MFMA operands; decode="fused" sends calls of 1..decode_max_tokens tokens to the
-single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead; linears that read the
+single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead, and decode="skinny"
+also those of up to skinny_max_tokens tokens to pt2q_ternary_skinny (csrc/ternary_skinny.hip:
+16x16x32 MFMA, x through LDS, the K-split reduced in the same launch); linears that read the
 same x go through pt2q_ternary_decode_group (the same kernel) in one launch, a gated MLP's gate
 and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp);
 the decode calls take an RMSNorm as prologue and a residual add as epilogue inside the same launch
@@ -28,7 +30,7 @@ import torch.nn.functional as F
 from . import _lib
 
 
-DECODE_MODES = ("mfma", "fused")
+DECODE_MODES = ("mfma", "fused", "skinny")
 # Largest token count a decode="fused" layer sends to pt2q_ternary_decode.  The library takes up to
 # pt2q_ternary_decode_max_tokens() = 8, but profiles/ternary_decode_timing.txt has the fused call
 # below the MFMA path at every measured shape and dtype only for 1 token (2 tokens lose by 0.19 us
@@ -54,6 +56,18 @@ mlp_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), ML
 # cover, and the block follows it.  A caller whose shapes do better may raise both, up to the cap.
 BLOCK_DECODE_CROSSOVER_TOKENS = 4
 block_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), BLOCK_DECODE_CROSSOVER_TOKENS)
+
+# Largest token count a decode="skinny" layer sends to pt2q_ternary_skinny (calls of
+# decode_max_tokens + 1 .. skinny_max_tokens tokens; below that range it routes as "fused" does).
+# The library takes up to pt2q_ternary_skinny_max_tokens() = 64; SKINNY_CROSSOVER_TOKENS is the
+# largest token count of profiles/ternary_skinny_timing.txt at which the skinny call is below the MFMA
+# path by more than the repeats' spread at every measured shape and dtype: measured,
+# that holds at 8, 16, 32 and 64 tokens (1.2 .. 16.2 us below), so the crossover is the cap.  At 2
+# and 4 tokens the call is 2.2 .. 3.8 us below at three of the four shapes and level with the MFMA
+# path (0.3 us below .. 0.1 us above) at 11008 x 4096; the module has one upper bound, so those counts
+# go to the new kernel as well.
+SKINNY_CROSSOVER_TOKENS = 64
+skinny_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_CROSSOVER_TOKENS)
 
 
 def _check_mode(decode):
@@ -129,6 +143,32 @@ def ternary_decode(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, a
         _lib.ptr(x), _lib.dtype_code(x), tokens, ldx, n, m, _lib.ptr(codes), _lib.ptr(gather),
         _lib.ptr(alpha), _lib.ptr(mu), B, bs, _lib.ptr(bias), _lib.ptr(out),
         _lib.dtype_code(out), ldy, _lib.stream_of(x.device)), "pt2q_ternary_decode")
+    return out
+
+
+def ternary_skinny(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, alpha: torch.Tensor,
+                   mu: torch.Tensor, block_size: int, bias: Optional[torch.Tensor] = None,
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """pt2q_ternary_skinny: y = x · Ŵᵀ (+ bias) for up to 64 tokens (the kernel for 2..64) on the
+    16x16x32 MFMA, the K-split reduced inside the GEMM launch; identical bits run to run.  x: tokens x m
+    fp16/bf16 with unit column stride (any row stride); codes (n x P/4 uint8) and gather (P int32)
+    from pt2q_ternary_pack; alpha, mu: n x B fp32; bias: n fp32 or None; out_dtype: x's dtype
+    (default) or torch.float32; out: an optional tokens x n tensor of that dtype with unit column
+    stride to write into."""
+    what = "ternary_skinny"
+    packs, bs = _group_members(x, [(codes, gather, alpha, mu, bias)], block_size, what)
+    codes, gather, alpha, mu, bias = packs[0]
+    tokens, m = x.shape
+    n, B = alpha.shape
+    out = _check_out(out, tokens, n, x.dtype if out_dtype is None else out_dtype, x.device, what)
+    if tokens == 0:
+        return out
+    lib = _lib.lib()
+    ws = _lib.workspace(lib.pt2q_ternary_skinny_workspace_bytes(tokens, n, m), x.device)
+    _lib.check(lib.pt2q_ternary_skinny(
+        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, n, m, _lib.ptr(codes),
+        _lib.ptr(gather), _lib.ptr(alpha), _lib.ptr(mu), B, bs, _lib.ptr(bias), _lib.ptr(out), _lib.dtype_code(out),
+        out.stride(0) if tokens > 1 else n, _lib.ptr(ws), ws.numel(), _lib.stream_of(x.device)), "pt2q_ternary_skinny")
     return out
 
 
@@ -254,7 +294,9 @@ def ternary_decode_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor]
 
 class TernaryLinear(nn.Module):
     """model.py:17-127.  decode="fused": forwards of 1..decode_max_tokens tokens run the
-    single-launch kernel (ternary_decode); every other call, and decode="mfma", the MFMA path."""
+    single-launch kernel (ternary_decode); decode="skinny": those as well, and forwards of
+    decode_max_tokens + 1 .. skinny_max_tokens tokens run ternary_skinny; every other call, and
+    decode="mfma", the MFMA path."""
 
     def __init__(self, in_features: int, out_features: int, block_size: int = 128,
                  bias: bool = True, dtype: torch.dtype = torch.float16, compat: bool = False,
@@ -337,8 +379,11 @@ class TernaryLinear(nn.Module):
         y = torch.empty((tokens, n), dtype=self.dtype, device=x.device)
         if tokens == 0:
             return y.reshape(*shape[:-1], n)
-        if self.decode == "fused" and tokens <= decode_max_tokens:
+        if self.decode in ("fused", "skinny") and tokens <= decode_max_tokens:
             ternary_decode(xt, codes, gather, a32, m32, self.block_size, b32, out=y)
+            return y.reshape(*shape[:-1], n)
+        if self.decode == "skinny" and tokens <= skinny_max_tokens:
+            ternary_skinny(xt, codes, gather, a32, m32, self.block_size, b32, out=y)
             return y.reshape(*shape[:-1], n)
         ws = _lib.workspace(_lib.lib().pt2q_ternary_linear_workspace_bytes(tokens, n, m), x.device)
         B = a32.shape[1]
@@ -501,7 +546,7 @@ def replace_linear_with_ternary(model: nn.Module, quantized_params: Dict[str, Di
 
 
 def set_decode(model: nn.Module, mode: str) -> nn.Module:
-    """Switch every TernaryLinear of `model` to decode="mfma" or "fused"."""
+    """Switch every TernaryLinear of `model` to decode="mfma", "fused" or "skinny"."""
     _check_mode(mode)
     for mod in model.modules():
         if isinstance(mod, TernaryLinear):
