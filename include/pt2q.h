@@ -440,6 +440,32 @@ int pt2q_ternary_decode_group(const void* x, int xdtype, int tokens, int64_t ldx
                               const float* const* bias /* array or entries nullable */,
                               void* const* y, int ydtype, const int64_t* ldy, int epilogue, void* stream);
 
+/* The grouped form of pt2q_ternary_skinny, for 2 .. 64 tokens: count (1 .. PT2Q_DECODE_GROUP_MAX)
+ * packed ternary linears that read the same x in ONE gather launch and ONE GEMM launch
+ * (csrc/ternary_skinny.hip): two launches, no synchronisation, capturable.  The argument list is
+ * pt2q_ternary_decode_group's plus the workspace of
+ * pt2q_ternary_skinny_group_workspace_bytes(tokens, m, count, n, epilogue) bytes (0 for arguments
+ * the call would refuse); the host arrays are read during the call only.  Per member the argument
+ * rules and status codes are pt2q_ternary_skinny's (1 .. 64 tokens, every codes[z] 8-byte aligned,
+ * the workspace 256-byte aligned, PT2Q_E_WORKSPACE when it is too small).  PT2Q_E_ARG: count outside
+ * 1 .. 4, an unknown epilogue, SWIGLU with count != 2, n[0] != n[1] or ydtype = PT2Q_F32.  Every
+ * check runs before anything is launched.  Nothing is read from what an earlier call left in the
+ * workspace.  Bit contract:
+ *   PT2Q_DECODE_PLAIN   y[z] holds what pt2q_ternary_skinny writes for member z alone, bit for bit
+ *                       (each member keeps the K split it has alone, and its partial sums are added
+ *                       in that call's fixed order), so it is identical run to run.
+ *   PT2Q_DECODE_SWIGLU  member 0 the gate, member 1 the up projection; only y[0] / ldy[0] are used:
+ *                       y[0] holds SWIGLU16 of the two lone calls' 16-bit outputs,
+ *                       RN_TY(RN_TY(g * sigmoid(g)) * u), bit for bit.  Non-finite g or u give an
+ *                       unspecified value. */
+size_t pt2q_ternary_skinny_group_workspace_bytes(int tokens, int m, int count, const int* n, int epilogue);
+int pt2q_ternary_skinny_group(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                              const int* n, const uint8_t* const* codes, const int* const* gather,
+                              const float* const* alpha, const float* const* mu, const int* B, int bs,
+                              const float* const* bias /* array or entries nullable */,
+                              void* const* y, int ydtype, const int64_t* ldy, int epilogue,
+                              void* workspace, size_t workspace_bytes, void* stream);
+
 /* y[t] = RMSNorm(x[t]) by contract RMSNORM16: the Llama form
  * weight * (x.float() * rsqrt(mean(x²) + eps)).to(xdtype), bit-defined -- 512 fmaf chains over the
  * elements i ≡ j (mod 512), a butterfly per 64 of them, the eight sums added in order, a correctly

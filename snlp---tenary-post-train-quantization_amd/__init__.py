@@ -13,6 +13,8 @@ Drop-in for the reference's hot-path surface:
     TernaryLinear, replace_linear_with_ternary                                     (model.py)
     ternary_decode, set_decode               (the fused 1-8 token decode kernel of TernaryLinear)
     ternary_skinny                           (the 2-64 token MFMA kernel, TernaryLinear(decode="skinny"))
+    ternary_skinny_group, ternary_skinny_swiglu
+                                             (its grouped form: projections sharing x, gate/up + SwiGLU, 2-64 tokens)
     ternary_decode_group, ternary_decode_swiglu, TernaryGatedMLP, fuse_gated_mlp
                                              (projections sharing x, and gate/up + SwiGLU, in one launch)
     rms_norm, TernaryMLPBlock                (RMSNorm as a kernel and as the decode kernel's prologue,
@@ -31,7 +33,8 @@ from .calibration import (GramAccumulator, GramCapture, find_linear_layers, get_
                           quantize_decoder_layer)
 from .ternary import (TernaryGatedMLP, TernaryLinear, TernaryMLPBlock, compute_bits_per_weight, fuse_gated_mlp,
                       load_quantized_model, replace_linear_with_ternary, rms_norm, save_quantized_model, set_decode,
-                      ternary_decode, ternary_decode_group, ternary_decode_swiglu, ternary_skinny)
+                      ternary_decode, ternary_decode_group, ternary_decode_swiglu, ternary_skinny,
+                      ternary_skinny_group, ternary_skinny_swiglu)
 from .evaluation import evaluate_perplexity
 from .engine import (LayerGraph, LayerOutput, LayerWorkspace, UnitRun, UnitWorkspace, cholesky_inverse,
                      dequantize, error_feedback, fill_synthetic, gram, hessian_inverse, pack_ternary, prepare_hessian,
@@ -52,5 +55,6 @@ __all__ = [
     "get_initial_reorder_indices", "SSRReorderer", "apply_permutation", "apply_permutation_to_input",
     "compute_block_variance", "LayerReport", "layer_report", "quadform_rows", "compute_output_error_from_gram",
     "ternary_decode", "set_decode", "ternary_decode_group", "ternary_decode_swiglu", "TernaryGatedMLP",
-    "fuse_gated_mlp", "rms_norm", "TernaryMLPBlock", "ternary_skinny",
+    "fuse_gated_mlp", "rms_norm", "TernaryMLPBlock", "ternary_skinny", "ternary_skinny_group",
+    "ternary_skinny_swiglu",
 ]

@@ -47,6 +47,7 @@
 
 #include "common.hpp"
 #include "internal.hpp"
+#include "ternary_shared.hpp"
 
 namespace {
 
@@ -61,42 +62,8 @@ constexpr int TD_LDS_PLAIN = 64 * 1024;      // dynamic LDS a launch gets withou
 constexpr int TD_LDS_MAX = 128 * 1024;       // what one token of the widest supported layer needs
 constexpr int TD_MAX_ROUNDS = 8;             // P <= 32768 positions: 64 KiB gathered + 64 KiB staged
 
-template <bool BF16>
-PT2Q_DEV uint32_t td_bits(float v) {  // RN to the activation dtype, as to_bits of ternary_linear.hip
-  uint16_t u;
-  if constexpr (BF16) {
-    __bf16 h = (__bf16)v;
-    __builtin_memcpy(&u, &h, 2);
-  } else {
-    _Float16 h = (_Float16)v;
-    __builtin_memcpy(&u, &h, 2);
-  }
-  return u;
-}
-
-// the low / high 16-bit element of a register, widened exactly to fp32
-template <bool BF16>
-PT2Q_DEV float td_lo(uint32_t u) {
-  if constexpr (BF16) {
-    return __uint_as_float(u << 16);
-  } else {
-    const uint16_t s = (uint16_t)(u & 0xffffu);
-    _Float16 h;
-    __builtin_memcpy(&h, &s, 2);
-    return (float)h;
-  }
-}
-template <bool BF16>
-PT2Q_DEV float td_hi(uint32_t u) {
-  if constexpr (BF16) {
-    return __uint_as_float(u & 0xffff0000u);
-  } else {
-    const uint16_t s = (uint16_t)(u >> 16);
-    _Float16 h;
-    __builtin_memcpy(&h, &s, 2);
-    return (float)h;
-  }
-}
+// td_bits, td_lo, td_hi (the exact 16-bit <-> fp32 conversions), td_pick and the SWIGLU16 arithmetic
+// (td_round, td_rounded, td_sigmoid, td_swiglu): ternary_shared.hpp, shared with ternary_skinny.hip
 
 // acc = fmaf((float)lo(w), (float)lo(x), acc) and the same for the high halves.  fp16 takes the
 // mixed-precision FMA, which widens both 16-bit operands inside the instruction (subnormals
@@ -194,61 +161,10 @@ struct TdGroup {  // the kernel's by-value argument: the members' host arrays, c
   int B[PT2Q_DECODE_GROUP_MAX];
   int wg_end[PT2Q_DECODE_GROUP_MAX];  // PLAIN: member z owns workgroups wg_end[z - 1] .. wg_end[z] - 1 of blockIdx.x
 };
-static_assert(PT2Q_DECODE_GROUP_MAX == 4, "td_pick and the member search name four entries");
-
 template <int Z>
 struct TdZ {
   static constexpr int value = Z;
 };
-
-// a[z] by selects: the argument arrays stay in the kernarg segment, nothing is indexed in memory
-template <class T>
-PT2Q_DEV T td_pick(const T (&a)[4], int z) {
-  T r = a[0];
-  if (z == 1) r = a[1];
-  if (z == 2) r = a[2];
-  if (z == 3) r = a[3];
-  return r;
-}
-
-template <bool BF16>
-PT2Q_DEV float td_round(float v) {  // RN_TY(v), widened back
-  return td_lo<BF16>(td_bits<BF16>(v));
-}
-
-// An fp32 product as a value of its own.  Without it the compiler folds RN_f16(g * q) into one
-// v_fma_mixlo_f16 with a +0 addend: a single rounding of the exact product where SWIGLU16 has two,
-// and +0 where the product is -0.
-PT2Q_DEV float td_rounded(float v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-// q of contract SWIGLU16: sigmoid(g) = (g >= 0 ? 1 : e) / (1 + e), e = exp(-|g|) by a degree-6
-// polynomial on the reduced argument.  fp32, every operation rounded on its own (-ffp-contract=off).
-PT2Q_DEV float td_sigmoid(float g) {
-  const float LOG2E = __uint_as_float(0x3FB8AA3Bu);
-  const float LN2_HI = __uint_as_float(0x3F317200u), LN2_LO = __uint_as_float(0x35BFBE8Eu);
-  const float C[7] = {__uint_as_float(0x3F800000u), __uint_as_float(0x3F800000u), __uint_as_float(0x3F000000u),
-                      __uint_as_float(0x3E2AA9FBu), __uint_as_float(0x3D2AAA2Du), __uint_as_float(0x3C093B5Eu),
-                      __uint_as_float(0x3AB6D7B4u)};
-  const float a = fabsf(g);
-  const float t = a * (-LOG2E);
-  float e = 0.0f;
-  if (!(t < -125.0f)) {
-    const float n = rintf(t);
-    float r = (-a) - n * LN2_HI;  // n * LN2_HI is exact: 7 bits by 15
-    r = r - n * LN2_LO;
-    float p = C[6];
-#pragma unroll
-    for (int k = 5; k >= 0; --k) {
-      p = p * r;
-      p = p + C[k];
-    }
-    e = ldexpf(p, (int)n);  // exact: n >= -125, p in [0.7, 1.42]
-  }
-  return (g >= 0.0f ? 1.0f : e) / (1.0f + e);
-}
 
 // What pt2q_ternary_decode_fused adds to a call, as a by-value argument of the kernels that take it
 // (tl_decode_fused_kernel, tl_decode_one_fused_kernel).  The kernels of the plain entries do not
@@ -529,8 +445,7 @@ PT2Q_DEV void td_decode(const uint16_t* x, long ldx, int tokens, int m, int P, i
         const bool st = lane == 0 && t0 + t < tokens;
         if constexpr (SWIGLU) {
           const float g = td_round<BF16>(biased(0, t)), u = td_round<BF16>(biased(1, t));
-          const float s = td_round<BF16>(td_rounded(g * td_sigmoid(g)));
-          const float h = td_rounded(s * u);
+          const float h = td_swiglu<BF16>(g, u);
           if (st) {
             if constexpr (BF16)
               ((__bf16*)G.y[0])[o] = (__bf16)h;

@@ -56,8 +56,20 @@
 // whichever workgroup is last, so the result is identical run to run -- converts and stores y.
 // Nobody waits for anybody: no spin, no grid sync.  The gather launch zeroes the counters, so
 // nothing depends on what an earlier call left in the workspace.  splits = 1 stores y directly.
+//
+// Grouped variant (pt2q_ternary_skinny_group; kernels and their comments below ts_kernel).  Up to
+// four layers that read the same x -- q/k/v, or a gated MLP's gate and up -- in ONE gather launch
+// (grid.y = member: each member has its own column order, so its own x_sel) and ONE GEMM launch whose
+// blockIdx.x walks the members' feature tiles one member after the other (at most three compares
+// against the tile prefix sums find the member).  Each member keeps the split count ts_plan gives it
+// alone, and the per-lane design above is untouched (ts_body is the one body of both kernels), so a
+// member's partial tiles and their sum are the lone call's, bit for bit.  SWIGLU reduces the gate
+// and the up tile of the same features under one shared ticket and applies contract SWIGLU16
+// (ternary_shared.hpp, the decode kernel's arithmetic) where the partials are summed anyway: the
+// fp32-to-16-bit stores of g and u, their re-reads and two elementwise launches disappear.
 #include "common.hpp"
 #include "internal.hpp"
+#include "ternary_shared.hpp"
 
 namespace {
 
@@ -152,20 +164,27 @@ PT2Q_DEV void ts_store4(TY* y, long ldy, int t, int i0, int n, bool vec, const f
   }
 }
 
-template <bool BF16, int NT, typename TY>
-__global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, const float* alpha, const float* mu,
-                                                 int B, int bse, const uint16_t* xs, int tokens, int n, int nP,
-                                                 int splits, float* part, int* cnt, const float* bias, TY* y,
-                                                 long ldy, int yvec) {
+// What the SWIGLU epilogue needs of the two members, gate then up (the grouped kernel's TsGroup entries)
+struct TsPair {
+  float* part[2];
+  const float* bias[2];
+  int splits[2];
+};
+
+// One workgroup's work, the body of the lone and of the grouped kernel: features fb .. fb + TS_F - 1
+// of one layer (n features, partial rows of nP floats, K slice z of `splits`, ticket counter *ticket).
+// SWIGLU (grouped kernel only): the layer is the gate or the up projection of `pair`, y is h.
+template <bool BF16, int NT, typename TY, bool SWIGLU>
+PT2Q_DEV void ts_body(const uint8_t* codes, int P, const float* alpha, const float* mu, int B, int bse,
+                      const uint16_t* xs, int tokens, int n, int nP, int splits, float* part, int* ticket,
+                      const float* bias, TY* y, long ldy, int yvec, int fb, int z, const TsPair& pair) {
   __shared__ __attribute__((aligned(1024))) uint8_t smem[TS_NS * TS_STG * NT];
   __shared__ int s_last;
   typedef __attribute__((address_space(3))) void* lptr;
   const int lane = threadIdx.x & 63;
   const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int r = lane & 15, kq = lane >> 4, h = kq & 1, gq = kq >> 1;
-  const int fb = blockIdx.x * TS_F;  // the workgroup's first feature
-  const int z = blockIdx.y;          // its K slice: blocks [kb0, kb1)
-  const int nkb = P / TS_PB;
+  const int nkb = P / TS_PB;  // slice z: blocks [kb0, kb1)
   const int kb0 = z * nkb / splits, kb1 = (z + 1) * nkb / splits;  // splits <= 16, nkb < 2^24
   const int nb = kb1 - kb0;
   // stage j (block kb0 + j) into ring slot j % TS_NS: 16-byte LDS slot S = (wv NT + q) 64 + lane is
@@ -292,7 +311,7 @@ __global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, co
     }
     ts_store4(y, ldy, 16 * u + r, i0, n, yvec != 0, v);
   };
-  if (splits == 1) {
+  if (!SWIGLU && splits == 1) {
 #pragma unroll
     for (int f = 0; f < TS_FT; ++f)
 #pragma unroll
@@ -304,7 +323,7 @@ __global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, co
     return;
   }
   // partial tile: part[z][t][i], rows of nP = tiles * TS_F floats, so every 16-byte store is inside
-  // (splits * tiles < 1024, so the byte offsets stay far below 2^31).  Agent-scope hand-off as in
+  // (the launchers keep splits * zs below 2^31).  Agent-scope hand-off as in
   // ssr.hip: write-through (sc1) stores, drained by every wave before the barrier that precedes
   // the ticket, and sc1 loads in the last workgroup -- they pass this XCD's L2 by, and no fence
   // writes back or invalidates a whole L2 under the other workgroups' x_sel and code lines.
@@ -321,9 +340,21 @@ __global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, co
     }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  if (threadIdx.x == 0) s_last = atomicAdd(cnt + blockIdx.x, 1) == splits - 1;
+  // SWIGLU: the gate and the up tile of these features share the counter, and both always get here
+  const int target = SWIGLU ? pair.splits[0] + pair.splits[1] : splits;
+  if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1) == target - 1;
   __syncthreads();
   if (!s_last) return;
+  // v = (p0 + p1) + ... over the `ns` slices of a fragment in rs, in slice order
+  auto sum = [&](const __amdgpu_buffer_rsrc_t rs, int ns, int off, float (&v)[4]) {
+    const f32x4 s4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16));
+    v[0] = s4[0], v[1] = s4[1], v[2] = s4[2], v[3] = s4[3];
+    for (int zz = 1; zz < ns; ++zz) {
+      const f32x4 p4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, zz * zs + off, 0, 16));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) v[q] = v[q] + p4[q];
+    }
+  };
 #pragma unroll
   for (int f = 0; f < TS_FT; ++f)
 #pragma unroll
@@ -331,15 +362,103 @@ __global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, co
       const int t = 16 * u + r;
       if (t >= tokens) continue;
       const int off = (t * nP + fb + (wv * TS_FT + f) * 16 + 4 * kq) * 4;
-      const f32x4 s4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, off, 0, 16));
-      float v[4] = {s4[0], s4[1], s4[2], s4[3]};
-      for (int zz = 1; zz < splits; ++zz) {
-        const f32x4 p4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rp, zz * zs + off, 0, 16));
+      if constexpr (!SWIGLU) {
+        float v[4];
+        sum(rp, splits, off, v);
+        finish(f, u, v);
+      } else {
+        // g and u as the two lone calls round them, then contract SWIGLU16 (td_swiglu leaves its last
+        // rounding to the store's conversion to TY)
+        const int i0 = fb + (wv * TS_FT + f) * 16 + 4 * kq;
+        float gv[4], uv[4];
+        sum(__builtin_amdgcn_make_buffer_rsrc(pair.part[0], 0, pair.splits[0] * zs, 0x00020000), pair.splits[0], off, gv);
+        sum(__builtin_amdgcn_make_buffer_rsrc(pair.part[1], 0, pair.splits[1] * zs, 0x00020000), pair.splits[1], off, uv);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) v[q] = v[q] + p4[q];
+        for (int q = 0; q < 4; ++q) {
+          if (i0 + q < n) {
+            if (pair.bias[0]) gv[q] = gv[q] + pair.bias[0][i0 + q];
+            if (pair.bias[1]) uv[q] = uv[q] + pair.bias[1][i0 + q];
+          }
+          gv[q] = td_swiglu<BF16>(td_round<BF16>(gv[q]), td_round<BF16>(uv[q]));
+        }
+        ts_store4(y, ldy, t, i0, n, yvec != 0, gv);
       }
-      finish(f, u, v);
     }
+}
+
+template <bool BF16, int NT, typename TY>
+__global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, const float* alpha, const float* mu,
+                                                 int B, int bse, const uint16_t* xs, int tokens, int n, int nP,
+                                                 int splits, float* part, int* cnt, const float* bias, TY* y,
+                                                 long ldy, int yvec) {
+  // blockIdx.x: the workgroup's 64-feature tile; blockIdx.y: its K slice
+  ts_body<BF16, NT, TY, false>(codes, P, alpha, mu, B, bse, xs, tokens, n, nP, splits, part, cnt + blockIdx.x, bias, y,
+                               ldy, yvec, blockIdx.x * TS_F, blockIdx.y, TsPair{});
+}
+
+// ---- The grouped variant: 1 .. 4 layers that read the same x in one gather and one GEMM launch.
+// The members' device pointers travel by value in the kernel arguments (TdGroup's way,
+// ternary_decode.hip); entries past the call's count repeat the last tile_end and own no workgroup.
+struct TsGroup {
+  const uint8_t* codes[PT2Q_DECODE_GROUP_MAX];
+  const float* alpha[PT2Q_DECODE_GROUP_MAX];
+  const float* mu[PT2Q_DECODE_GROUP_MAX];
+  const float* bias[PT2Q_DECODE_GROUP_MAX];
+  void* y[PT2Q_DECODE_GROUP_MAX];
+  long ldy[PT2Q_DECODE_GROUP_MAX];
+  float* part[PT2Q_DECODE_GROUP_MAX];  // the member's partial tiles
+  int n[PT2Q_DECODE_GROUP_MAX];
+  int B[PT2Q_DECODE_GROUP_MAX];
+  int splits[PT2Q_DECODE_GROUP_MAX];    // ts_plan's for the member alone
+  int yvec[PT2Q_DECODE_GROUP_MAX];
+  int tile_end[PT2Q_DECODE_GROUP_MAX];  // member z owns blockIdx.x in [tile_end[z - 1], tile_end[z])
+};
+struct TsGatherGroup {
+  const int* g[PT2Q_DECODE_GROUP_MAX];
+};
+
+// x_sel[z][t][p] = x[t][g_z[p]] for member z = blockIdx.y (every linear has its own order of the
+// columns, so the members cannot share one x_sel); the call's ncnt ticket counters to 0
+__global__ void ts_gather_group_kernel(const uint16_t* x, long ldx, int tokens, TsGatherGroup G, int P, uint16_t* xs,
+                                       long xs_stride, int* cnt, int ncnt) {
+  const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (blockIdx.y == 0)
+    for (long c = q; c < ncnt; c += (long)gridDim.x * blockDim.x) cnt[c] = 0;
+  if (q >= (long)tokens * P) return;
+  const int t = (int)(q / P), p = (int)(q % P);
+  const int c = td_pick(G.g, (int)blockIdx.y)[p];
+  xs[blockIdx.y * xs_stride + q] = (c >= 0) ? x[(long)t * ldx + c] : (uint16_t)0;
+}
+
+// blockIdx.x walks the members' 64-feature tiles one member after the other, blockIdx.y is the K
+// slice.  Member z runs with the split count it has alone, so its workgroups compute the lone
+// kernel's partial tiles bit for bit; workgroups of a slice its member does not have leave at once.
+//   PLAIN   one counter per (member, tile): ts_body as the lone kernel runs it.
+//   SWIGLU  gate tile i and up tile i share counter i, target splits_gate + splits_up, and both
+//           members always write partials; the workgroup that draws the last ticket sums both
+//           members' slices in slice order, rounds g and u as the lone calls store them and writes
+//           h by contract SWIGLU16 (td_swiglu).  Nobody waits: the same hand-off as PLAIN.
+template <bool BF16, int NT, typename TY, bool SWIGLU>
+__global__ __launch_bounds__(256) void ts_group_kernel(int P, int bse, const uint16_t* xs, long xs_stride, int tokens,
+                                                       int* cnt, TsGroup G) {
+  int z = 0, t0 = 0;
+#pragma unroll
+  for (int j = 0; j < PT2Q_DECODE_GROUP_MAX - 1; ++j) {
+    if ((int)blockIdx.x >= G.tile_end[j]) {
+      z = j + 1;
+      t0 = G.tile_end[j];
+    }
+  }
+  const int splits = td_pick(G.splits, z);
+  if ((int)blockIdx.y >= splits) return;
+  const int bx = blockIdx.x - t0;  // the member's tile
+  const int nP = (td_pick(G.tile_end, z) - t0) * TS_F;
+  const int zy = SWIGLU ? 0 : z;  // whose y the workgroup may write
+  ts_body<BF16, NT, TY, SWIGLU>(td_pick(G.codes, z), P, td_pick(G.alpha, z), td_pick(G.mu, z), td_pick(G.B, z), bse,
+                                xs + z * xs_stride, tokens, td_pick(G.n, z), nP, splits, td_pick(G.part, z),
+                                cnt + (SWIGLU ? bx : (int)blockIdx.x), td_pick(G.bias, z), (TY*)td_pick(G.y, zy),
+                                td_pick(G.ldy, zy), td_pick(G.yvec, zy), bx * TS_F, blockIdx.y,
+                                TsPair{{G.part[0], G.part[1]}, {G.bias[0], G.bias[1]}, {G.splits[0], G.splits[1]}});
 }
 
 // Launch plan shared by the workspace query and the launcher (rule and reasons: header comment)
@@ -377,6 +496,54 @@ void ts_launch(const TsPlan& pl, hipStream_t st, const uint8_t* codes, const flo
     case 2: go(ts_kernel<BF16, 2, TY>); break;
     case 3: go(ts_kernel<BF16, 3, TY>); break;
     default: go(ts_kernel<BF16, 4, TY>); break;
+  }
+}
+
+// The grouped call's plan, shared by its workspace query and its launcher: every member's own
+// ts_plan, and the workspace as count x_sel images, the counters (PLAIN: one per tile of every
+// member; SWIGLU: one per tile of the gate), then the members' partial tiles (SWIGLU: always).
+struct TsGroupPlan {
+  TsPlan mem[PT2Q_DECODE_GROUP_MAX];
+  bool swiglu;
+  int tiles, max_splits, ncnt;
+  size_t cnt_bytes, part_off[PT2Q_DECODE_GROUP_MAX], total;
+};
+// false for a call the entry refuses (and the query answers with 0)
+bool ts_group_plan(int tokens, int m, int count, const int* n, int epilogue, TsGroupPlan& g) {
+  if (tokens <= 0 || tokens > TS_MAX_TOKENS || m <= 0 || !n || count < 1 || count > PT2Q_DECODE_GROUP_MAX) return false;
+  g.swiglu = epilogue == PT2Q_DECODE_SWIGLU;
+  if (!g.swiglu && epilogue != PT2Q_DECODE_PLAIN) return false;
+  if (g.swiglu && (count != 2 || n[0] != n[1])) return false;
+  g.tiles = 0, g.max_splits = 1;
+  size_t parts = 0;
+  for (int z = 0; z < count; ++z) {
+    if (n[z] <= 0) return false;
+    TsPlan& p = g.mem[z] = ts_plan(tokens, n[z], m);
+    if (g.swiglu) p.part_bytes = (size_t)p.splits * tokens * p.tiles * TS_F * 4;
+    if (p.part_bytes >= ((size_t)1 << 31)) return false;  // the kernels' 32-bit byte offsets
+    g.part_off[z] = parts;
+    parts += p.part_bytes;
+    g.tiles += p.tiles;
+    if (p.splits > g.max_splits) g.max_splits = p.splits;
+  }
+  g.ncnt = g.swiglu ? g.mem[0].tiles : g.tiles;
+  g.cnt_bytes = ((size_t)g.ncnt * 4 + 255) / 256 * 256;
+  g.total = (size_t)count * g.mem[0].xs_bytes + g.cnt_bytes + parts + 256;
+  return true;
+}
+
+template <bool BF16, typename TY, bool SWIGLU>
+void ts_group_launch(const TsGroupPlan& g, hipStream_t st, int bse, const uint16_t* xs, int tokens, int* cnt,
+                     const TsGroup& G) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(g.tiles, g.max_splits), dim3(256), 0, st, g.mem[0].P, bse, xs,
+                       (long)(g.mem[0].xs_bytes / 2), tokens, cnt, G);
+  };
+  switch (g.mem[0].NT) {
+    case 1: go(ts_group_kernel<BF16, 1, TY, SWIGLU>); break;
+    case 2: go(ts_group_kernel<BF16, 2, TY, SWIGLU>); break;
+    case 3: go(ts_group_kernel<BF16, 3, TY, SWIGLU>); break;
+    default: go(ts_group_kernel<BF16, 4, TY, SWIGLU>); break;
   }
 }
 
@@ -426,6 +593,82 @@ extern "C" int pt2q_ternary_skinny(const void* x, int xdtype, int tokens, int64_
   } else {
     ts_launch<false, _Float16>(pl, st, codes, alpha, mu, B, bse, xs, tokens, n, part, cnt, bias, (_Float16*)y,
                                (long)ldy);
+  }
+  PT2Q_LAUNCH_CHECK();
+  return PT2Q_OK;
+}
+
+extern "C" size_t pt2q_ternary_skinny_group_workspace_bytes(int tokens, int m, int count, const int* n, int epilogue) {
+  TsGroupPlan g;
+  return ts_group_plan(tokens, m, count, n, epilogue, g) ? g.total : 0;
+}
+
+extern "C" int pt2q_ternary_skinny_group(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                                         const int* n, const uint8_t* const* codes, const int* const* gather,
+                                         const float* const* alpha, const float* const* mu, const int* B, int bs,
+                                         const float* const* bias, void* const* y, int ydtype, const int64_t* ldy,
+                                         int epilogue, void* workspace, size_t workspace_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !n || !codes || !gather || !alpha || !mu || !B || !y || !ldy || tokens <= 0 || m <= 0 || ldx < m ||
+      bs <= 0 || count < 1 || count > PT2Q_DECODE_GROUP_MAX)
+    return PT2Q_E_ARG;
+  const bool swiglu = epilogue == PT2Q_DECODE_SWIGLU;
+  if (!swiglu && epilogue != PT2Q_DECODE_PLAIN) return PT2Q_E_ARG;
+  if (swiglu && (count != 2 || n[0] != n[1] || ydtype == PT2Q_F32)) return PT2Q_E_ARG;
+  const int nout = swiglu ? 1 : count;  // outputs the call writes
+  for (int z = 0; z < count; ++z) {
+    if (!codes[z] || !gather[z] || !alpha[z] || !mu[z] || n[z] <= 0 || B[z] <= 0) return PT2Q_E_ARG;
+    if (z < nout && (!y[z] || ldy[z] < n[z])) return PT2Q_E_ARG;
+  }
+  if (xdtype != PT2Q_F16 && xdtype != PT2Q_BF16) return PT2Q_E_UNSUPPORTED;
+  if (ydtype != xdtype && ydtype != PT2Q_F32) return PT2Q_E_ARG;
+  if (tokens > TS_MAX_TOKENS) return PT2Q_E_UNSUPPORTED;
+  if (bs < m && bs % 16 != 0) return PT2Q_E_UNSUPPORTED;  // alpha constant within a 16-group
+  for (int z = 0; z < count; ++z)
+    if ((long)ceil_div(m, bs < m ? bs : m) > B[z]) return PT2Q_E_ARG;
+  for (int z = 0; z < count; ++z)
+    if ((uintptr_t)codes[z] % 8 != 0) return PT2Q_E_UNSUPPORTED;
+  if (!workspace || (uintptr_t)workspace % 256 != 0) return PT2Q_E_UNSUPPORTED;
+  TsGroupPlan g;
+  if (!ts_group_plan(tokens, m, count, n, epilogue, g)) return PT2Q_E_UNSUPPORTED;
+  if (workspace_bytes < g.total) return PT2Q_E_WORKSPACE;
+  const int P = g.mem[0].P;
+  const int bse = bs < m ? bs : P;  // per-channel: one scale for every position
+  uint16_t* xs = (uint16_t*)workspace;
+  int* cnt = (int*)((char*)workspace + (size_t)count * g.mem[0].xs_bytes);
+  char* parts = (char*)cnt + g.cnt_bytes;
+  const size_t ysize = ydtype == PT2Q_F32 ? 4 : 2;
+  TsGroup G{};
+  TsGatherGroup GG{};
+  int tile_end = 0;
+  for (int z = 0; z < PT2Q_DECODE_GROUP_MAX; ++z) {
+    const int s = z < count ? z : 0;  // entries past count repeat member 0 and own no workgroup
+    if (z < count) tile_end += g.mem[z].tiles;
+    G.codes[z] = codes[s], G.alpha[z] = alpha[s], G.mu[z] = mu[s], G.bias[z] = bias ? bias[s] : nullptr;
+    G.n[z] = n[s], G.B[z] = B[s], G.splits[z] = g.mem[s].splits, G.tile_end[z] = tile_end;
+    G.part[z] = (float*)(parts + g.part_off[s]);
+    G.y[z] = s < nout ? y[s] : nullptr, G.ldy[z] = s < nout ? (long)ldy[s] : 0;
+    G.yvec[z] = (s < nout && (uintptr_t)y[s] % (4 * ysize) == 0 && ldy[s] % 4 == 0) ? 1 : 0;
+    GG.g[z] = gather[s];
+  }
+  hipLaunchKernelGGL(ts_gather_group_kernel, dim3(ceil_div((long)tokens * P, 256), count), dim3(256), 0, st,
+                     (const uint16_t*)x, (long)ldx, tokens, GG, P, xs, (long)(g.mem[0].xs_bytes / 2), cnt, g.ncnt);
+  PT2Q_LAUNCH_CHECK();
+  const bool bf16 = xdtype == PT2Q_BF16;
+  if (swiglu) {
+    if (bf16)
+      ts_group_launch<true, __bf16, true>(g, st, bse, xs, tokens, cnt, G);
+    else
+      ts_group_launch<false, _Float16, true>(g, st, bse, xs, tokens, cnt, G);
+  } else if (ydtype == PT2Q_F32) {
+    if (bf16)
+      ts_group_launch<true, float, false>(g, st, bse, xs, tokens, cnt, G);
+    else
+      ts_group_launch<false, float, false>(g, st, bse, xs, tokens, cnt, G);
+  } else if (bf16) {
+    ts_group_launch<true, __bf16, false>(g, st, bse, xs, tokens, cnt, G);
+  } else {
+    ts_group_launch<false, _Float16, false>(g, st, bse, xs, tokens, cnt, G);
   }
   PT2Q_LAUNCH_CHECK();
   return PT2Q_OK;

@@ -7,7 +7,9 @@ pt2q_ternary_linear (csrc/ternary_linear.hip): 2-bit packed codes dequantised in
 f16/bf16 MFMA operands; decode="fused" sends calls of 1..decode_max_tokens tokens to the
 single-launch kernel pt2q_ternary_decode (csrc/ternary_decode.hip) instead, and decode="skinny"
 also those of up to skinny_max_tokens tokens to pt2q_ternary_skinny (csrc/ternary_skinny.hip:
-16x16x32 MFMA, x through LDS, the K-split reduced in the same launch); linears that read the
+16x16x32 MFMA, x through LDS, the K-split reduced in the same launch; its grouped form
+pt2q_ternary_skinny_group runs q/k/v, or gate and up with SwiGLU, in one gather and one GEMM
+launch: ternary_skinny_group, ternary_skinny_swiglu); linears that read the
 same x go through pt2q_ternary_decode_group (the same kernel) in one launch, a gated MLP's gate
 and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp);
 the decode calls take an RMSNorm as prologue and a residual add as epilogue inside the same launch
@@ -68,6 +70,16 @@ block_decode_max_tokens = min(int(_lib.lib().pt2q_ternary_decode_max_tokens()), 
 # go to the new kernel as well.
 SKINNY_CROSSOVER_TOKENS = 64
 skinny_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_CROSSOVER_TOKENS)
+# Largest token count a TernaryGatedMLP whose children are all decode="skinny" runs as
+# ternary_skinny_swiglu + ternary_skinny(down_proj) (calls of mlp_decode_max_tokens + 1 ..
+# skinny_mlp_max_tokens tokens); above it the children are called one by one.
+# SKINNY_MLP_CROSSOVER_TOKENS is the largest token count of profiles/ternary_skinny_group_timing.txt
+# up to which that two-call form is below down(F.silu(gate(x)) * up(x)) over skinny children by more
+# than the repeats' spread at every measured shape and dtype.  Measured (hidden 4096 /
+# 11008 and 5120 / 13824, fp16 and bf16, 2 .. 64 tokens): 11.4 .. 16.4 us below at every count, spread at
+# most 0.14 us, so the crossover is the cap.  A caller may lower it; the library takes no more than 64.
+SKINNY_MLP_CROSSOVER_TOKENS = 64
+skinny_mlp_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_MLP_CROSSOVER_TOKENS)
 
 
 def _check_mode(decode):
@@ -292,6 +304,59 @@ def ternary_decode_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor]
     return out
 
 
+def _skinny_group(x, packs, block_size, outs, epilogue):
+    """pt2q_ternary_skinny_group on checked members: one gather launch and one GEMM launch."""
+    tokens, m = x.shape
+    count = len(packs)
+    lib = _lib.lib()
+    ns = (ctypes.c_int * count)(*[p[2].shape[0] for p in packs])
+    Bs = (ctypes.c_int * count)(*[p[2].shape[1] for p in packs])
+    ldys = (ctypes.c_int64 * len(outs))(*[t.stride(0) if tokens > 1 else t.shape[1] for t in outs])
+    arrs = [_lib.ptr_array([p[i] for p in packs]) for i in range(5)] + [_lib.ptr_array(outs)]
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    ws = _lib.workspace(lib.pt2q_ternary_skinny_group_workspace_bytes(tokens, m, count, as_p(ns), epilogue), x.device)
+    _lib.check(lib.pt2q_ternary_skinny_group(
+        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns), arrs[0][0],
+        arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0], _lib.dtype_code(outs[0]),
+        as_p(ldys), epilogue, _lib.ptr(ws), ws.numel(), _lib.stream_of(x.device)), "pt2q_ternary_skinny_group")
+
+
+def ternary_skinny_group(x: torch.Tensor, members, out_dtype: Optional[torch.dtype] = None, outs=None,
+                         block_size: Optional[int] = None):
+    """pt2q_ternary_skinny_group, PLAIN: 1..4 ternary linears on the same x (up to 64 tokens; the
+    kernel for 2..64) in one gather launch and one GEMM launch -- q/k/v of a batched-decode or
+    speculative step.  members, out_dtype, outs and block_size as in ternary_decode_group.  Returns
+    one tokens x n tensor per member, each bit-equal to ternary_skinny on that member alone."""
+    what = "ternary_skinny_group"
+    packs, bs = _group_members(x, members, block_size, what)
+    tokens = x.shape[0]
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if outs is not None and len(outs) != len(packs):
+        raise _lib.Pt2qError(f"{what}: one out per member")
+    outs = [_check_out(None if outs is None else outs[z], tokens, p[2].shape[0], out_dtype, x.device, what)
+            for z, p in enumerate(packs)]
+    if tokens:
+        _skinny_group(x, packs, bs, outs, _lib.DECODE_PLAIN)
+    return outs
+
+
+def ternary_skinny_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor] = None,
+                          block_size: Optional[int] = None) -> torch.Tensor:
+    """pt2q_ternary_skinny_group, SWIGLU: h = silu(gate(x)) * up(x) for up to 64 tokens in one gather
+    launch and one GEMM launch, the activation computed where the K-split partials are summed;
+    bit-defined by contract SWIGLU16 from the 16-bit outputs the two separate
+    ternary_skinny calls would give.  gate, up: members as in ternary_decode_group, equal widths; h
+    has x's dtype."""
+    what = "ternary_skinny_swiglu"
+    packs, bs = _group_members(x, [gate, up], block_size, what)
+    if packs[0][2].shape[0] != packs[1][2].shape[0]:
+        raise _lib.Pt2qError(f"{what}: gate and up have the same number of rows")
+    out = _check_out(out, x.shape[0], packs[0][2].shape[0], x.dtype, x.device, what)
+    if x.shape[0]:
+        _skinny_group(x, packs, bs, [out], _lib.DECODE_SWIGLU)
+    return out
+
+
 class TernaryLinear(nn.Module):
     """model.py:17-127.  decode="fused": forwards of 1..decode_max_tokens tokens run the
     single-launch kernel (ternary_decode); decode="skinny": those as well, and forwards of
@@ -421,8 +486,10 @@ class TernaryGatedMLP(nn.Module):
     """down_proj(silu(gate_proj(x)) * up_proj(x)) over three TernaryLinear children (the names, and
     so the state_dict keys, of a Llama MLP).  With all three at decode="fused", forwards of
     1..mlp_decode_max_tokens tokens take two launches -- ternary_decode_swiglu, then
-    ternary_decode on down_proj -- in place of three launches and two elementwise kernels; every
-    other call goes through the children exactly as the unfused MLP does."""
+    ternary_decode on down_proj -- in place of three launches and two elementwise kernels.  With
+    all three at decode="skinny", forwards of mlp_decode_max_tokens + 1 .. skinny_mlp_max_tokens
+    tokens are ternary_skinny_swiglu, then ternary_skinny on down_proj (four launches in place of
+    eight).  Every other call goes through the children exactly as the unfused MLP does."""
 
     def __init__(self, gate_proj: TernaryLinear, up_proj: TernaryLinear, down_proj: TernaryLinear):
         super().__init__()
@@ -441,6 +508,15 @@ class TernaryGatedMLP(nn.Module):
                 h = ternary_decode_swiglu(xt, gate, up)
                 codes, gather, a32, m32, b32 = down._packed
                 y = ternary_decode(h, codes, gather, a32, m32, down.block_size, b32)
+                return y.reshape(*x.shape[:-1], down.out_features)
+        if gate.decode == up.decode == down.decode == "skinny":
+            xt = x.reshape(-1, gate.in_features).to(gate.dtype).contiguous()
+            if mlp_decode_max_tokens < xt.shape[0] <= skinny_mlp_max_tokens:
+                if down._packed is None:
+                    down._prepare()
+                h = ternary_skinny_swiglu(xt, gate, up)
+                codes, gather, a32, m32, b32 = down._packed
+                y = ternary_skinny(h, codes, gather, a32, m32, down.block_size, b32)
                 return y.reshape(*x.shape[:-1], down.out_features)
         return down(F.silu(gate(x)) * up(x))
 
