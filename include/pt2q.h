@@ -499,6 +499,33 @@ int pt2q_ternary_decode_fused(const void* x, int xdtype, int tokens, int64_t ldx
                               const void* const* residual /* array or entries nullable */,
                               const int64_t* ldr, void* stream);
 
+/* pt2q_ternary_skinny_group with an RMSNorm prologue and a residual epilogue, for 2 .. 64 tokens,
+ * still two launches with no synchronisation and no allocation (csrc/ternary_skinny.hip): the norm
+ * runs in the gather launch, the residual is added where the K-split partials are summed and y is
+ * converted.  The workspace is that of pt2q_ternary_skinny_group_workspace_bytes; the norm needs none.
+ *   norm_weight  NULL, or m elements of xdtype: the members read RMSNORM16(x, norm_weight, norm_eps)
+ *                in place of x, with the bits pt2q_rmsnorm would have written (x itself is not
+ *                written).  PLAIN and SWIGLU.  m > 32768 with a norm weight is PT2Q_E_UNSUPPORTED
+ *                (the normalised row is held in 64 KiB of LDS).
+ *   residual     NULL, or a host array with one entry per output, each NULL or tokens x n[z] of
+ *                ydtype with leading dimension ldr[z] >= n[z]: y[z] = RN_TY(f32(RN_TY(v + bias)) +
+ *                f32(residual[z])), contract RESADD16 -- the bits of residual + (the call without
+ *                it) as an elementwise 16-bit add gives them.  residual[z] may be y[z] itself.
+ *                PLAIN only, ydtype = xdtype.
+ * All rules of pt2q_ternary_skinny_group hold.  PT2Q_E_ARG: norm_weight with an eps that is negative,
+ * infinite or NaN; a residual entry with ydtype = PT2Q_F32, with SWIGLU, with ldr NULL or
+ * ldr[z] < n[z].  Every check runs before anything is launched.  With norm_weight NULL and no
+ * residual entry the call is pt2q_ternary_skinny_group, bit for bit; a group of one has the bits of
+ * pt2q_ternary_skinny. */
+int pt2q_ternary_skinny_fused(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                              const int* n, const uint8_t* const* codes, const int* const* gather,
+                              const float* const* alpha, const float* const* mu, const int* B, int bs,
+                              const float* const* bias /* array or entries nullable */,
+                              void* const* y, int ydtype, const int64_t* ldy, int epilogue,
+                              const void* norm_weight, float norm_eps,
+                              const void* const* residual /* array or entries nullable */,
+                              const int64_t* ldr, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

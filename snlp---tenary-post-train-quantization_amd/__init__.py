@@ -14,7 +14,9 @@ Drop-in for the reference's hot-path surface:
     ternary_decode, set_decode               (the fused 1-8 token decode kernel of TernaryLinear)
     ternary_skinny                           (the 2-64 token MFMA kernel, TernaryLinear(decode="skinny"))
     ternary_skinny_group, ternary_skinny_swiglu
-                                             (its grouped form: projections sharing x, gate/up + SwiGLU, 2-64 tokens)
+                                             (its grouped form: projections sharing x, gate/up + SwiGLU, 2-64 tokens;
+                                              norm= and residual(s)= on all three: RMSNorm in the gather launch,
+                                              the residual add where y is converted)
     ternary_decode_group, ternary_decode_swiglu, TernaryGatedMLP, fuse_gated_mlp
                                              (projections sharing x, and gate/up + SwiGLU, in one launch)
     rms_norm, TernaryMLPBlock                (RMSNorm as a kernel and as the decode kernel's prologue,

@@ -108,6 +108,7 @@ _SIGS = {
     "pt2q_ternary_skinny_group": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, SZ, P]),
     "pt2q_rmsnorm": (I, [P, I, I, I64, I, P, F, P, I64, P]),
     "pt2q_ternary_decode_fused": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, F, P, P, P]),
+    "pt2q_ternary_skinny_fused": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, F, P, P, P, SZ, P]),
 }
 for _name, (_res, _args) in _SIGS.items():
     _fn = getattr(_h, _name)

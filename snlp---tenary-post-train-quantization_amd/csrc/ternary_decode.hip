@@ -179,23 +179,9 @@ struct TdExtra {
 // residual epilogue where the use has one (not SWIGLU).
 enum TdFx { TD_FX_NONE, TD_FX_RES, TD_FX_NORM };
 
-// r of contract RMSNORM16 from the eight wave sums of a row's squares: the sums
-// added in order, then a division, an add, a square root and a division, each the correctly
-// rounded fp32 operation (hipcc's default for / and sqrtf; no fast-math, no contraction).
-PT2Q_DEV float td_norm_r(const float* sums, int m, float eps) {
-  float ss = sums[0];
-#pragma unroll
-  for (int k = 1; k < TD_WAVES; ++k) ss = ss + sums[k];
-  const float mean = ss / (float)m;
-  return 1.0f / sqrtf(mean + eps);
-}
-// RN_TX(RN_TX(xf * r) * wf): both products fp32 values of their own (td_rounded)
-template <bool BF16>
-PT2Q_DEV uint16_t td_normed(uint32_t xu, uint32_t wu, float r) {
-  const float xn = td_round<BF16>(td_rounded(td_lo<BF16>(xu) * r));
-  return (uint16_t)td_bits<BF16>(td_rounded(xn * td_lo<BF16>(wu)));
-}
-constexpr int TD_NORM_PREFETCH = 16;  // weight elements a thread loads ahead of the sums' barrier: m <= 8192
+// td_norm_r, td_normed (contract RMSNORM16) and TD_NORM_PREFETCH: ternary_shared.hpp, shared with the
+// skinny kernel's normalising gather
+static_assert(TD_WAVES == TD_NORM_SUMS, "RMSNORM16 has one sum per wave of the workgroup");
 
 // The kernel's body: all of a workgroup's work for the group G.
 template <bool BF16, int TG, bool SWIGLU, TdFx FX>

@@ -1,7 +1,7 @@
-// What the ternary decode kernel (ternary_decode.hip) and the skinny kernel's grouped variant
-// (ternary_skinny.hip) share: the exact 16-bit <-> fp32 conversions, the arithmetic of contract
-// SWIGLU16, and the select that reads one member's entry of a by-value group argument.
-// One definition, so the two kernels' SwiGLU epilogues cannot drift apart.
+// What the ternary decode kernel (ternary_decode.hip) and the skinny kernels (ternary_skinny.hip)
+// share: the exact 16-bit <-> fp32 conversions, the arithmetic of contracts SWIGLU16 and RMSNORM16
+// (DESIGN.md §3), and the select that reads one member's entry of a by-value group argument.
+// One definition, so the two files' SwiGLU epilogues and norm prologues cannot drift apart.
 #pragma once
 #include "common.hpp"
 
@@ -103,5 +103,24 @@ PT2Q_DEV float td_swiglu(float g, float u) {
   const float s = td_round<BF16>(td_rounded(g * td_sigmoid(g)));
   return td_rounded(s * u);
 }
+
+// r of contract RMSNORM16 from the eight wave sums of a row's squares: the sums
+// added in order, then a division, an add, a square root and a division, each the correctly
+// rounded fp32 operation (hipcc's default for / and sqrtf; no fast-math, no contraction).
+constexpr int TD_NORM_SUMS = 8;  // 512 chains in waves of 64
+PT2Q_DEV float td_norm_r(const float* sums, int m, float eps) {
+  float ss = sums[0];
+#pragma unroll
+  for (int k = 1; k < TD_NORM_SUMS; ++k) ss = ss + sums[k];
+  const float mean = ss / (float)m;
+  return 1.0f / sqrtf(mean + eps);
+}
+// RN_TX(RN_TX(xf * r) * wf): both products fp32 values of their own (td_rounded)
+template <bool BF16>
+PT2Q_DEV uint16_t td_normed(uint32_t xu, uint32_t wu, float r) {
+  const float xn = td_round<BF16>(td_rounded(td_lo<BF16>(xu) * r));
+  return (uint16_t)td_bits<BF16>(td_rounded(xn * td_lo<BF16>(wu)));
+}
+constexpr int TD_NORM_PREFETCH = 16;  // elements a thread loads ahead of the sums' barrier: all of them for m <= 8192
 
 }  // namespace

@@ -67,6 +67,19 @@
 // and the up tile of the same features under one shared ticket and applies contract SWIGLU16
 // (ternary_shared.hpp, the decode kernel's arithmetic) where the partials are summed anyway: the
 // fp32-to-16-bit stores of g and u, their re-reads and two elementwise launches disappear.
+//
+// Norm prologue and residual epilogue (pt2q_ternary_skinny_fused), still two launches.  The gather
+// already reads every element of x, so contract RMSNORM16 runs there: ts_norm_gather_kernel, one
+// 512-thread workgroup per (token, member), normalises the row into a 2 m-byte LDS image and gathers
+// x_sel from LDS (its comment has the steps; m <= 32768).  The residual belongs where y is converted:
+// ts_body's RES flag adds contract RESADD16 to finish(), on the direct path and in the last-ticket
+// workgroup, whose lanes ask for the residual of exactly the elements they will store (so it may be y
+// itself) before they walk the partial slices.  The flag is off in ts_kernel and ts_group_kernel, whose
+// instructions are what they were; ts_group_res_kernel is the PLAIN grouped kernel with it on and the
+// residual pointers as one more by-value argument.  Both contracts' arithmetic is the decode kernel's
+// (ternary_shared.hpp), so the bits are those of pt2q_rmsnorm, the plain call and a 16-bit add.
+#include <cfloat>
+
 #include "common.hpp"
 #include "internal.hpp"
 #include "ternary_shared.hpp"
@@ -164,6 +177,22 @@ PT2Q_DEV void ts_store4(TY* y, long ldy, int t, int i0, int n, bool vec, const f
   }
 }
 
+// The residual of the four elements ts_store4 will store for this lane, two per register, +0 where it
+// stores nothing: one 8-byte load where res allows it (vec: base and ldr aligned to four elements),
+// element loads at a ragged edge.  A lane reads what it will write and nothing else: res may be y.
+PT2Q_DEV u32x2 ts_res4(const uint16_t* res, long ldr, int t, int i0, int n, bool vec) {
+  const uint16_t* p = res + (long)t * ldr + i0;
+  u32x2 w = {0u, 0u};
+  if (vec && i0 + 3 < n) {
+    w = *(const u32x2*)p;
+  } else {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (i0 + q < n) w[q >> 1] |= (uint32_t)p[q] << (16 * (q & 1));
+  }
+  return w;
+}
+
 // What the SWIGLU epilogue needs of the two members, gate then up (the grouped kernel's TsGroup entries)
 struct TsPair {
   float* part[2];
@@ -174,10 +203,15 @@ struct TsPair {
 // One workgroup's work, the body of the lone and of the grouped kernel: features fb .. fb + TS_F - 1
 // of one layer (n features, partial rows of nP floats, K slice z of `splits`, ticket counter *ticket).
 // SWIGLU (grouped kernel only): the layer is the gate or the up projection of `pair`, y is h.
-template <bool BF16, int NT, typename TY, bool SWIGLU>
+// RES (pt2q_ternary_skinny_fused, PLAIN, 16-bit y): contract RESADD16 where y is converted, on the
+// direct path and in the last-ticket workgroup, y = RN_TY(f32(RN_TY(v + bias)) + f32(res)); res NULL
+// for a member without a residual.  With RES off res, ldr and rvec are not looked at.
+template <bool BF16, int NT, typename TY, bool SWIGLU, bool RES>
 PT2Q_DEV void ts_body(const uint8_t* codes, int P, const float* alpha, const float* mu, int B, int bse,
                       const uint16_t* xs, int tokens, int n, int nP, int splits, float* part, int* ticket,
-                      const float* bias, TY* y, long ldy, int yvec, int fb, int z, const TsPair& pair) {
+                      const float* bias, TY* y, long ldy, int yvec, int fb, int z, const TsPair& pair,
+                      const uint16_t* res, long ldr, int rvec) {
+  static_assert(!RES || (!SWIGLU && sizeof(TY) == 2), "RESADD16 is 16-bit and h has no residual");
   __shared__ __attribute__((aligned(1024))) uint8_t smem[TS_NS * TS_STG * NT];
   __shared__ int s_last;
   typedef __attribute__((address_space(3))) void* lptr;
@@ -302,16 +336,39 @@ PT2Q_DEV void ts_body(const uint8_t* codes, int P, const float* alpha, const flo
     }
   }
   // D[feature 4 kq + q][token r]: the lane holds features i0 .. i0 + 3 of token 16 u + r
-  auto finish = [&](int f, int u, float (&v)[4]) {  // + bias, convert, store
+  // RES: the residual of what the lane will store, asked for ahead of the sums it is added to
+  u32x2 rr[TS_FT][NT];
+  auto load_res = [&]() {
+    if constexpr (RES) {
+#pragma unroll
+      for (int f = 0; f < TS_FT; ++f)
+#pragma unroll
+        for (int u = 0; u < NT; ++u) {
+          rr[f][u] = u32x2{0u, 0u};
+          if (res && 16 * u + r < tokens)
+            rr[f][u] = ts_res4(res, ldr, 16 * u + r, fb + (wv * TS_FT + f) * 16 + 4 * kq, n, rvec != 0);
+        }
+    }
+  };
+  auto finish = [&](int f, int u, float (&v)[4]) {  // + bias, (+ residual,) convert, store
     const int i0 = fb + (wv * TS_FT + f) * 16 + 4 * kq;
     if (bias) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         if (i0 + q < n) v[q] = v[q] + bias[i0 + q];
     }
+    if constexpr (RES) {
+      if (res) {
+        const u32x2 w = rr[f][u];
+        const float rf[4] = {td_lo<BF16>(w[0]), td_hi<BF16>(w[0]), td_lo<BF16>(w[1]), td_hi<BF16>(w[1])};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] = td_rounded(td_round<BF16>(v[q]) + rf[q]);
+      }
+    }
     ts_store4(y, ldy, 16 * u + r, i0, n, yvec != 0, v);
   };
   if (!SWIGLU && splits == 1) {
+    load_res();
 #pragma unroll
     for (int f = 0; f < TS_FT; ++f)
 #pragma unroll
@@ -345,6 +402,7 @@ PT2Q_DEV void ts_body(const uint8_t* codes, int P, const float* alpha, const flo
   if (threadIdx.x == 0) s_last = atomicAdd(ticket, 1) == target - 1;
   __syncthreads();
   if (!s_last) return;
+  load_res();  // in flight under the sc1 loads of the partial slices
   // v = (p0 + p1) + ... over the `ns` slices of a fragment in rs, in slice order
   auto sum = [&](const __amdgpu_buffer_rsrc_t rs, int ns, int off, float (&v)[4]) {
     const f32x4 s4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, 16));
@@ -392,8 +450,8 @@ __global__ __launch_bounds__(256) void ts_kernel(const uint8_t* codes, int P, co
                                                  int splits, float* part, int* cnt, const float* bias, TY* y,
                                                  long ldy, int yvec) {
   // blockIdx.x: the workgroup's 64-feature tile; blockIdx.y: its K slice
-  ts_body<BF16, NT, TY, false>(codes, P, alpha, mu, B, bse, xs, tokens, n, nP, splits, part, cnt + blockIdx.x, bias, y,
-                               ldy, yvec, blockIdx.x * TS_F, blockIdx.y, TsPair{});
+  ts_body<BF16, NT, TY, false, false>(codes, P, alpha, mu, B, bse, xs, tokens, n, nP, splits, part, cnt + blockIdx.x,
+                                      bias, y, ldy, yvec, blockIdx.x * TS_F, blockIdx.y, TsPair{}, nullptr, 0, 0);
 }
 
 // ---- The grouped variant: 1 .. 4 layers that read the same x in one gather and one GEMM launch.
@@ -430,6 +488,104 @@ __global__ void ts_gather_group_kernel(const uint16_t* x, long ldx, int tokens, 
   xs[blockIdx.y * xs_stride + q] = (c >= 0) ? x[(long)t * ldx + c] : (uint16_t)0;
 }
 
+// The grouped gather with contract RMSNORM16 in front of it, for
+// pt2q_ternary_skinny_fused with a norm weight: x_sel[z][t][p] = rmsnorm(x)[t][g_z[p]], the bits
+// pt2q_rmsnorm would have written, and x itself is never written.  One workgroup of 512 threads serves
+// token t = blockIdx.x for the members z = blockIdx.y, blockIdx.y + gridDim.y, ...:
+//   1. thread j runs the fmaf chain of squares over the elements i ≡ j (mod 512), ascending from +0
+//      (partial j of RMSNORM16), keeping its first TD_NORM_PREFETCH elements of x and of the weight in
+//      registers (16-bit loads: x has any 2-byte-aligned base and any ldx); bfly64 per wave, the eight
+//      wave sums through the head of the LDS image, td_norm_r in every thread;
+//   2. every thread writes td_normed of the elements it read into the 2 m-byte LDS image of the
+//      normalised row (elements past its registers are read again, from the cache);
+//   3. after one barrier the workgroup gathers from LDS, eight consecutive positions per thread:
+//      two 16-byte loads of g (the first pair issued before step 1), eight 16-bit LDS reads (padding
+//      positions g < 0 give 0), one 16-byte store into x_sel[z][t][.].
+// The launcher's grid is tokens x count: the norm is computed once per member, because at 2 tokens
+// the launch is bound by its latency chain and not by its arithmetic.  The alternative, tokens x 1
+// with every workgroup looping over the members (make EXTRA_HIPFLAGS=-DPT2Q_TS_NORM_LOOP=1), was timed
+// against it: profiles/ternary_skinny_block_timing.txt.  The image caps the prologue at m <= 32768.
+#ifndef PT2Q_TS_NORM_LOOP
+#define PT2Q_TS_NORM_LOOP 0
+#endif
+constexpr int TS_NG_THREADS = TD_NORM_SUMS * 64;
+constexpr int TS_NG_MAX_M = 32768;  // 64 KiB of dynamic LDS
+
+template <bool BF16>
+__global__ __launch_bounds__(TS_NG_THREADS) void ts_norm_gather_kernel(const uint16_t* x, long ldx, int m,
+                                                                       const uint16_t* nw, float eps, TsGatherGroup G,
+                                                                       int count, int P, uint16_t* xs, long xs_stride,
+                                                                       int* cnt, int ncnt) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t ts_img[];
+  const int tid = threadIdx.x, t = blockIdx.x;
+  if (blockIdx.y == 0)
+    for (int c = t * TS_NG_THREADS + tid; c < ncnt; c += gridDim.x * TS_NG_THREADS) cnt[c] = 0;
+  const uint16_t* xr = x + (long)t * ldx;
+  uint32_t xc[TD_NORM_PREFETCH], wc[TD_NORM_PREFETCH];
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    const int i = tid + j * TS_NG_THREADS;
+    xc[j] = i < m ? xr[i] : 0u;
+    wc[j] = i < m ? nw[i] : 0u;
+  }
+  auto load_gi = [&](const int* g, int o, int (&gi)[8]) {  // g[8 o .. 8 o + 7], nothing past P
+    if (o >= P / 8) return;
+    if (((uintptr_t)g & 15) == 0) {
+      const int4 g0 = *(const int4*)(g + 8 * o), g1 = *(const int4*)(g + 8 * o + 4);
+      gi[0] = g0.x, gi[1] = g0.y, gi[2] = g0.z, gi[3] = g0.w;
+      gi[4] = g1.x, gi[5] = g1.y, gi[6] = g1.z, gi[7] = g1.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) gi[j] = g[8 * o + j];
+    }
+  };
+  int gn[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  load_gi(td_pick(G.g, (int)blockIdx.y), tid, gn);
+  float acc = 0.0f;
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    if (tid + j * TS_NG_THREADS < m) {
+      const float xf = td_lo<BF16>(xc[j]);
+      acc = fmaf(xf, xf, acc);
+    }
+  }
+  for (int i = tid + TD_NORM_PREFETCH * TS_NG_THREADS; i < m; i += TS_NG_THREADS) {
+    const float xf = td_lo<BF16>(xr[i]);
+    acc = fmaf(xf, xf, acc);
+  }
+  acc = bfly64(acc);
+  if ((tid & 63) == 0) ((float*)ts_img)[tid >> 6] = acc;
+  __syncthreads();
+  const float r = td_norm_r((const float*)ts_img, m, eps);
+  __syncthreads();  // every thread has the sums: the image may take their place
+  uint16_t* img = (uint16_t*)ts_img;
+#pragma unroll
+  for (int j = 0; j < TD_NORM_PREFETCH; ++j) {
+    const int i = tid + j * TS_NG_THREADS;
+    if (i < m) img[i] = td_normed<BF16>(xc[j], wc[j], r);
+  }
+  for (int i = tid + TD_NORM_PREFETCH * TS_NG_THREADS; i < m; i += TS_NG_THREADS) img[i] = td_normed<BF16>(xr[i], nw[i], r);
+  __syncthreads();
+  for (int z = blockIdx.y; z < count; z += gridDim.y) {
+    const int* g = td_pick(G.g, z);
+    if (z != (int)blockIdx.y) load_gi(g, tid, gn);
+    uint16_t* dst = xs + z * xs_stride + (long)t * P;
+    for (int o = tid; o < P / 8; o += TS_NG_THREADS) {  // positions 8 o .. 8 o + 7
+      int gi[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) gi[j] = gn[j];
+      load_gi(g, o + TS_NG_THREADS, gn);
+      uint32_t e[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) e[j] = gi[j] >= 0 ? (uint32_t)img[gi[j]] : 0u;
+      u32x4 v;
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) v[jj] = e[2 * jj] | (e[2 * jj + 1] << 16);
+      *(u32x4*)(dst + 8 * o) = v;
+    }
+  }
+}
+
 // blockIdx.x walks the members' 64-feature tiles one member after the other, blockIdx.y is the K
 // slice.  Member z runs with the split count it has alone, so its workgroups compute the lone
 // kernel's partial tiles bit for bit; workgroups of a slice its member does not have leave at once.
@@ -438,9 +594,17 @@ __global__ void ts_gather_group_kernel(const uint16_t* x, long ldx, int tokens, 
 //           members always write partials; the workgroup that draws the last ticket sums both
 //           members' slices in slice order, rounds g and u as the lone calls store them and writes
 //           h by contract SWIGLU16 (td_swiglu).  Nobody waits: the same hand-off as PLAIN.
-template <bool BF16, int NT, typename TY, bool SWIGLU>
-__global__ __launch_bounds__(256) void ts_group_kernel(int P, int bse, const uint16_t* xs, long xs_stride, int tokens,
-                                                       int* cnt, TsGroup G) {
+// TsRes (pt2q_ternary_skinny_fused): the members' residuals, a by-value argument of the kernel that
+// takes one (ts_group_res_kernel).  ts_group_kernel does not carry it: its arguments and its code are
+// what they were.
+struct TsRes {
+  const uint16_t* res[PT2Q_DECODE_GROUP_MAX];  // RESADD16: per member, NULL for none
+  long ldr[PT2Q_DECODE_GROUP_MAX];
+  int rvec[PT2Q_DECODE_GROUP_MAX];
+};
+template <bool BF16, int NT, typename TY, bool SWIGLU, bool RES>
+PT2Q_DEV void ts_group_body(int P, int bse, const uint16_t* xs, long xs_stride, int tokens, int* cnt, const TsGroup& G,
+                            const TsRes& R) {
   int z = 0, t0 = 0;
 #pragma unroll
   for (int j = 0; j < PT2Q_DECODE_GROUP_MAX - 1; ++j) {
@@ -454,11 +618,26 @@ __global__ __launch_bounds__(256) void ts_group_kernel(int P, int bse, const uin
   const int bx = blockIdx.x - t0;  // the member's tile
   const int nP = (td_pick(G.tile_end, z) - t0) * TS_F;
   const int zy = SWIGLU ? 0 : z;  // whose y the workgroup may write
-  ts_body<BF16, NT, TY, SWIGLU>(td_pick(G.codes, z), P, td_pick(G.alpha, z), td_pick(G.mu, z), td_pick(G.B, z), bse,
-                                xs + z * xs_stride, tokens, td_pick(G.n, z), nP, splits, td_pick(G.part, z),
-                                cnt + (SWIGLU ? bx : (int)blockIdx.x), td_pick(G.bias, z), (TY*)td_pick(G.y, zy),
-                                td_pick(G.ldy, zy), td_pick(G.yvec, zy), bx * TS_F, blockIdx.y,
-                                TsPair{{G.part[0], G.part[1]}, {G.bias[0], G.bias[1]}, {G.splits[0], G.splits[1]}});
+  const uint16_t* res = nullptr;
+  long ldr = 0;
+  int rvec = 0;
+  if constexpr (RES) res = td_pick(R.res, z), ldr = td_pick(R.ldr, z), rvec = td_pick(R.rvec, z);
+  ts_body<BF16, NT, TY, SWIGLU, RES>(
+      td_pick(G.codes, z), P, td_pick(G.alpha, z), td_pick(G.mu, z), td_pick(G.B, z), bse, xs + z * xs_stride, tokens,
+      td_pick(G.n, z), nP, splits, td_pick(G.part, z), cnt + (SWIGLU ? bx : (int)blockIdx.x), td_pick(G.bias, z),
+      (TY*)td_pick(G.y, zy), td_pick(G.ldy, zy), td_pick(G.yvec, zy), bx * TS_F, blockIdx.y,
+      TsPair{{G.part[0], G.part[1]}, {G.bias[0], G.bias[1]}, {G.splits[0], G.splits[1]}}, res, ldr, rvec);
+}
+template <bool BF16, int NT, typename TY, bool SWIGLU>
+__global__ __launch_bounds__(256) void ts_group_kernel(int P, int bse, const uint16_t* xs, long xs_stride, int tokens,
+                                                       int* cnt, TsGroup G) {
+  ts_group_body<BF16, NT, TY, SWIGLU, false>(P, bse, xs, xs_stride, tokens, cnt, G, TsRes{});
+}
+// PLAIN with contract RESADD16 at the members' stores (16-bit y)
+template <bool BF16, int NT, typename TY>
+__global__ __launch_bounds__(256) void ts_group_res_kernel(int P, int bse, const uint16_t* xs, long xs_stride,
+                                                           int tokens, int* cnt, TsGroup G, TsRes R) {
+  ts_group_body<BF16, NT, TY, false, true>(P, bse, xs, xs_stride, tokens, cnt, G, R);
 }
 
 // Launch plan shared by the workspace query and the launcher (rule and reasons: header comment)
@@ -547,6 +726,125 @@ void ts_group_launch(const TsGroupPlan& g, hipStream_t st, int bse, const uint16
   }
 }
 
+// the same grid for PLAIN with residuals
+template <bool BF16, typename TY>
+void ts_group_res_launch(const TsGroupPlan& g, hipStream_t st, int bse, const uint16_t* xs, int tokens, int* cnt,
+                         const TsGroup& G, const TsRes& R) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(g.tiles, g.max_splits), dim3(256), 0, st, g.mem[0].P, bse, xs,
+                       (long)(g.mem[0].xs_bytes / 2), tokens, cnt, G, R);
+  };
+  switch (g.mem[0].NT) {
+    case 1: go(ts_group_res_kernel<BF16, 1, TY>); break;
+    case 2: go(ts_group_res_kernel<BF16, 2, TY>); break;
+    case 3: go(ts_group_res_kernel<BF16, 3, TY>); break;
+    default: go(ts_group_res_kernel<BF16, 4, TY>); break;
+  }
+}
+
+// pt2q_ternary_skinny_group and pt2q_ternary_skinny_fused (norm_weight and residual NULL from the
+// former): every check, then the gather launch and the GEMM launch.
+int ts_group_call(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count, const int* n,
+                  const uint8_t* const* codes, const int* const* gather, const float* const* alpha,
+                  const float* const* mu, const int* B, int bs, const float* const* bias, void* const* y, int ydtype,
+                  const int64_t* ldy, int epilogue, const void* norm_weight, float norm_eps,
+                  const void* const* residual, const int64_t* ldr, void* workspace, size_t workspace_bytes,
+                  void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!x || !n || !codes || !gather || !alpha || !mu || !B || !y || !ldy || tokens <= 0 || m <= 0 || ldx < m ||
+      bs <= 0 || count < 1 || count > PT2Q_DECODE_GROUP_MAX)
+    return PT2Q_E_ARG;
+  const bool swiglu = epilogue == PT2Q_DECODE_SWIGLU;
+  if (!swiglu && epilogue != PT2Q_DECODE_PLAIN) return PT2Q_E_ARG;
+  if (swiglu && (count != 2 || n[0] != n[1] || ydtype == PT2Q_F32)) return PT2Q_E_ARG;
+  const int nout = swiglu ? 1 : count;  // outputs the call writes
+  for (int z = 0; z < count; ++z) {
+    if (!codes[z] || !gather[z] || !alpha[z] || !mu[z] || n[z] <= 0 || B[z] <= 0) return PT2Q_E_ARG;
+    if (z < nout && (!y[z] || ldy[z] < n[z])) return PT2Q_E_ARG;
+  }
+  if (norm_weight && !(norm_eps >= 0.0f && norm_eps <= FLT_MAX)) return PT2Q_E_ARG;  // finite, not NaN
+  bool anyres = false;
+  for (int z = 0; residual && z < nout; ++z) {
+    if (!residual[z]) continue;
+    if (swiglu || ydtype == PT2Q_F32 || !ldr || ldr[z] < n[z]) return PT2Q_E_ARG;  // RESADD16 is 16-bit, and h has no residual
+    anyres = true;
+  }
+  if (xdtype != PT2Q_F16 && xdtype != PT2Q_BF16) return PT2Q_E_UNSUPPORTED;
+  if (ydtype != xdtype && ydtype != PT2Q_F32) return PT2Q_E_ARG;
+  if (tokens > TS_MAX_TOKENS) return PT2Q_E_UNSUPPORTED;
+  if (bs < m && bs % 16 != 0) return PT2Q_E_UNSUPPORTED;  // alpha constant within a 16-group
+  for (int z = 0; z < count; ++z)
+    if ((long)ceil_div(m, bs < m ? bs : m) > B[z]) return PT2Q_E_ARG;
+  for (int z = 0; z < count; ++z)
+    if ((uintptr_t)codes[z] % 8 != 0) return PT2Q_E_UNSUPPORTED;
+  if (!workspace || (uintptr_t)workspace % 256 != 0) return PT2Q_E_UNSUPPORTED;
+  if (norm_weight && m > TS_NG_MAX_M) return PT2Q_E_UNSUPPORTED;  // the normalised row's LDS image
+  TsGroupPlan g;
+  if (!ts_group_plan(tokens, m, count, n, epilogue, g)) return PT2Q_E_UNSUPPORTED;
+  if (workspace_bytes < g.total) return PT2Q_E_WORKSPACE;
+  const int P = g.mem[0].P;
+  const int bse = bs < m ? bs : P;  // per-channel: one scale for every position
+  uint16_t* xs = (uint16_t*)workspace;
+  int* cnt = (int*)((char*)workspace + (size_t)count * g.mem[0].xs_bytes);
+  char* parts = (char*)cnt + g.cnt_bytes;
+  const size_t ysize = ydtype == PT2Q_F32 ? 4 : 2;
+  TsGroup G{};
+  TsGatherGroup GG{};
+  TsRes R{};
+  int tile_end = 0;
+  for (int z = 0; z < PT2Q_DECODE_GROUP_MAX; ++z) {
+    const int s = z < count ? z : 0;  // entries past count repeat member 0 and own no workgroup
+    if (z < count) tile_end += g.mem[z].tiles;
+    G.codes[z] = codes[s], G.alpha[z] = alpha[s], G.mu[z] = mu[s], G.bias[z] = bias ? bias[s] : nullptr;
+    G.n[z] = n[s], G.B[z] = B[s], G.splits[z] = g.mem[s].splits, G.tile_end[z] = tile_end;
+    G.part[z] = (float*)(parts + g.part_off[s]);
+    G.y[z] = s < nout ? y[s] : nullptr, G.ldy[z] = s < nout ? (long)ldy[s] : 0;
+    G.yvec[z] = (s < nout && (uintptr_t)y[s] % (4 * ysize) == 0 && ldy[s] % 4 == 0) ? 1 : 0;
+    GG.g[z] = gather[s];
+    const bool r = anyres && s < nout && residual[s];
+    R.res[z] = r ? (const uint16_t*)residual[s] : nullptr, R.ldr[z] = r ? (long)ldr[s] : 0;
+    R.rvec[z] = (r && (uintptr_t)residual[s] % 8 == 0 && ldr[s] % 4 == 0) ? 1 : 0;
+  }
+  const bool bf16 = xdtype == PT2Q_BF16;
+  const long xs_stride = (long)(g.mem[0].xs_bytes / 2);
+  if (norm_weight) {
+    const dim3 grid(tokens, PT2Q_TS_NORM_LOOP ? 1 : count);
+    const size_t lds = ((size_t)m * 2 + 15) / 16 * 16 < 32 ? 32 : ((size_t)m * 2 + 15) / 16 * 16;  // the sums, then the image
+    if (bf16)
+      hipLaunchKernelGGL(ts_norm_gather_kernel<true>, grid, dim3(TS_NG_THREADS), lds, st, (const uint16_t*)x, (long)ldx,
+                         m, (const uint16_t*)norm_weight, norm_eps, GG, count, P, xs, xs_stride, cnt, g.ncnt);
+    else
+      hipLaunchKernelGGL(ts_norm_gather_kernel<false>, grid, dim3(TS_NG_THREADS), lds, st, (const uint16_t*)x, (long)ldx,
+                         m, (const uint16_t*)norm_weight, norm_eps, GG, count, P, xs, xs_stride, cnt, g.ncnt);
+  } else {
+    hipLaunchKernelGGL(ts_gather_group_kernel, dim3(ceil_div((long)tokens * P, 256), count), dim3(256), 0, st,
+                       (const uint16_t*)x, (long)ldx, tokens, GG, P, xs, xs_stride, cnt, g.ncnt);
+  }
+  PT2Q_LAUNCH_CHECK();
+  if (swiglu) {
+    if (bf16)
+      ts_group_launch<true, __bf16, true>(g, st, bse, xs, tokens, cnt, G);
+    else
+      ts_group_launch<false, _Float16, true>(g, st, bse, xs, tokens, cnt, G);
+  } else if (ydtype == PT2Q_F32) {
+    if (bf16)
+      ts_group_launch<true, float, false>(g, st, bse, xs, tokens, cnt, G);
+    else
+      ts_group_launch<false, float, false>(g, st, bse, xs, tokens, cnt, G);
+  } else if (anyres) {
+    if (bf16)
+      ts_group_res_launch<true, __bf16>(g, st, bse, xs, tokens, cnt, G, R);
+    else
+      ts_group_res_launch<false, _Float16>(g, st, bse, xs, tokens, cnt, G, R);
+  } else if (bf16) {
+    ts_group_launch<true, __bf16, false>(g, st, bse, xs, tokens, cnt, G);
+  } else {
+    ts_group_launch<false, _Float16, false>(g, st, bse, xs, tokens, cnt, G);
+  }
+  PT2Q_LAUNCH_CHECK();
+  return PT2Q_OK;
+}
+
 }  // namespace
 
 extern "C" int pt2q_ternary_skinny_max_tokens(void) { return TS_MAX_TOKENS; }
@@ -608,68 +906,19 @@ extern "C" int pt2q_ternary_skinny_group(const void* x, int xdtype, int tokens, 
                                          const float* const* alpha, const float* const* mu, const int* B, int bs,
                                          const float* const* bias, void* const* y, int ydtype, const int64_t* ldy,
                                          int epilogue, void* workspace, size_t workspace_bytes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (!x || !n || !codes || !gather || !alpha || !mu || !B || !y || !ldy || tokens <= 0 || m <= 0 || ldx < m ||
-      bs <= 0 || count < 1 || count > PT2Q_DECODE_GROUP_MAX)
-    return PT2Q_E_ARG;
-  const bool swiglu = epilogue == PT2Q_DECODE_SWIGLU;
-  if (!swiglu && epilogue != PT2Q_DECODE_PLAIN) return PT2Q_E_ARG;
-  if (swiglu && (count != 2 || n[0] != n[1] || ydtype == PT2Q_F32)) return PT2Q_E_ARG;
-  const int nout = swiglu ? 1 : count;  // outputs the call writes
-  for (int z = 0; z < count; ++z) {
-    if (!codes[z] || !gather[z] || !alpha[z] || !mu[z] || n[z] <= 0 || B[z] <= 0) return PT2Q_E_ARG;
-    if (z < nout && (!y[z] || ldy[z] < n[z])) return PT2Q_E_ARG;
-  }
-  if (xdtype != PT2Q_F16 && xdtype != PT2Q_BF16) return PT2Q_E_UNSUPPORTED;
-  if (ydtype != xdtype && ydtype != PT2Q_F32) return PT2Q_E_ARG;
-  if (tokens > TS_MAX_TOKENS) return PT2Q_E_UNSUPPORTED;
-  if (bs < m && bs % 16 != 0) return PT2Q_E_UNSUPPORTED;  // alpha constant within a 16-group
-  for (int z = 0; z < count; ++z)
-    if ((long)ceil_div(m, bs < m ? bs : m) > B[z]) return PT2Q_E_ARG;
-  for (int z = 0; z < count; ++z)
-    if ((uintptr_t)codes[z] % 8 != 0) return PT2Q_E_UNSUPPORTED;
-  if (!workspace || (uintptr_t)workspace % 256 != 0) return PT2Q_E_UNSUPPORTED;
-  TsGroupPlan g;
-  if (!ts_group_plan(tokens, m, count, n, epilogue, g)) return PT2Q_E_UNSUPPORTED;
-  if (workspace_bytes < g.total) return PT2Q_E_WORKSPACE;
-  const int P = g.mem[0].P;
-  const int bse = bs < m ? bs : P;  // per-channel: one scale for every position
-  uint16_t* xs = (uint16_t*)workspace;
-  int* cnt = (int*)((char*)workspace + (size_t)count * g.mem[0].xs_bytes);
-  char* parts = (char*)cnt + g.cnt_bytes;
-  const size_t ysize = ydtype == PT2Q_F32 ? 4 : 2;
-  TsGroup G{};
-  TsGatherGroup GG{};
-  int tile_end = 0;
-  for (int z = 0; z < PT2Q_DECODE_GROUP_MAX; ++z) {
-    const int s = z < count ? z : 0;  // entries past count repeat member 0 and own no workgroup
-    if (z < count) tile_end += g.mem[z].tiles;
-    G.codes[z] = codes[s], G.alpha[z] = alpha[s], G.mu[z] = mu[s], G.bias[z] = bias ? bias[s] : nullptr;
-    G.n[z] = n[s], G.B[z] = B[s], G.splits[z] = g.mem[s].splits, G.tile_end[z] = tile_end;
-    G.part[z] = (float*)(parts + g.part_off[s]);
-    G.y[z] = s < nout ? y[s] : nullptr, G.ldy[z] = s < nout ? (long)ldy[s] : 0;
-    G.yvec[z] = (s < nout && (uintptr_t)y[s] % (4 * ysize) == 0 && ldy[s] % 4 == 0) ? 1 : 0;
-    GG.g[z] = gather[s];
-  }
-  hipLaunchKernelGGL(ts_gather_group_kernel, dim3(ceil_div((long)tokens * P, 256), count), dim3(256), 0, st,
-                     (const uint16_t*)x, (long)ldx, tokens, GG, P, xs, (long)(g.mem[0].xs_bytes / 2), cnt, g.ncnt);
-  PT2Q_LAUNCH_CHECK();
-  const bool bf16 = xdtype == PT2Q_BF16;
-  if (swiglu) {
-    if (bf16)
-      ts_group_launch<true, __bf16, true>(g, st, bse, xs, tokens, cnt, G);
-    else
-      ts_group_launch<false, _Float16, true>(g, st, bse, xs, tokens, cnt, G);
-  } else if (ydtype == PT2Q_F32) {
-    if (bf16)
-      ts_group_launch<true, float, false>(g, st, bse, xs, tokens, cnt, G);
-    else
-      ts_group_launch<false, float, false>(g, st, bse, xs, tokens, cnt, G);
-  } else if (bf16) {
-    ts_group_launch<true, __bf16, false>(g, st, bse, xs, tokens, cnt, G);
-  } else {
-    ts_group_launch<false, _Float16, false>(g, st, bse, xs, tokens, cnt, G);
-  }
-  PT2Q_LAUNCH_CHECK();
-  return PT2Q_OK;
+  return ts_group_call(x, xdtype, tokens, ldx, m, count, n, codes, gather, alpha, mu, B, bs, bias, y, ydtype, ldy,
+                       epilogue, nullptr, 0.0f, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+// The group entry with the RMSNorm prologue (in the gather launch) and the residual epilogue (where y
+// is converted).  A call that asks for neither launches what pt2q_ternary_skinny_group launches.
+extern "C" int pt2q_ternary_skinny_fused(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                                         const int* n, const uint8_t* const* codes, const int* const* gather,
+                                         const float* const* alpha, const float* const* mu, const int* B, int bs,
+                                         const float* const* bias, void* const* y, int ydtype, const int64_t* ldy,
+                                         int epilogue, const void* norm_weight, float norm_eps,
+                                         const void* const* residual, const int64_t* ldr, void* workspace,
+                                         size_t workspace_bytes, void* stream) {
+  return ts_group_call(x, xdtype, tokens, ldx, m, count, n, codes, gather, alpha, mu, B, bs, bias, y, ydtype, ldy,
+                       epilogue, norm_weight, norm_eps, residual, ldr, workspace, workspace_bytes, stream);
 }

@@ -13,7 +13,8 @@ launch: ternary_skinny_group, ternary_skinny_swiglu); linears that read the
 same x go through pt2q_ternary_decode_group (the same kernel) in one launch, a gated MLP's gate
 and up projection with the SwiGLU activation as its epilogue (TernaryGatedMLP, fuse_gated_mlp);
 the decode calls take an RMSNorm as prologue and a residual add as epilogue inside the same launch
-(norm=, residual=, pt2q_ternary_decode_fused; rms_norm; TernaryMLPBlock).
+(norm=, residual=, pt2q_ternary_decode_fused; rms_norm; TernaryMLPBlock), and so do the skinny
+calls inside their two launches (pt2q_ternary_skinny_fused).
 Two semantics:
 
   compat=False (default)  y = x · Ŵᵀ + b with the correct reconstruction of gptq.py:201-230
@@ -80,6 +81,18 @@ skinny_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY
 # most 0.14 us, so the crossover is the cap.  A caller may lower it; the library takes no more than 64.
 SKINNY_MLP_CROSSOVER_TOKENS = 64
 skinny_mlp_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_MLP_CROSSOVER_TOKENS)
+# Largest token count a TernaryMLPBlock whose projections are all decode="skinny" runs as
+# ternary_skinny_swiglu with the norm in its gather launch + ternary_skinny(down_proj) with h as
+# residual (calls of min(block_decode_max_tokens, mlp_decode_max_tokens) + 1 .. skinny_block_max_tokens
+# tokens: four launches); above it the block is rms_norm, the TernaryGatedMLP and torch's add (six).
+# SKINNY_BLOCK_CROSSOVER_TOKENS is the largest token count of profiles/ternary_skinny_block_timing.txt up
+# to which the two-call form is below that six-launch form, as the parent commit ran it, by more than
+# the repeats' spread at every measured shape and dtype.  Measured (hidden 4096 /
+# 11008 and 5120 / 13824, fp16 and bf16, 2 .. 64 tokens): 0.4 .. 3.2 us below at every count (the
+# smallest margin, 0.44 us, at 5120 / 13824 fp16 with 2 tokens), spread at most 0.05 us, so the
+# crossover is the cap.  A caller may lower it; the library takes no more than 64.
+SKINNY_BLOCK_CROSSOVER_TOKENS = 64
+skinny_block_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_BLOCK_CROSSOVER_TOKENS)
 
 
 def _check_mode(decode):
@@ -160,19 +173,26 @@ def ternary_decode(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, a
 
 def ternary_skinny(x: torch.Tensor, codes: torch.Tensor, gather: torch.Tensor, alpha: torch.Tensor,
                    mu: torch.Tensor, block_size: int, bias: Optional[torch.Tensor] = None,
-                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                   out_dtype: Optional[torch.dtype] = None, out: Optional[torch.Tensor] = None,
+                   norm=None, residual: Optional[torch.Tensor] = None) -> torch.Tensor:
     """pt2q_ternary_skinny: y = x · Ŵᵀ (+ bias) for up to 64 tokens (the kernel for 2..64) on the
     16x16x32 MFMA, the K-split reduced inside the GEMM launch; identical bits run to run.  x: tokens x m
     fp16/bf16 with unit column stride (any row stride); codes (n x P/4 uint8) and gather (P int32)
     from pt2q_ternary_pack; alpha, mu: n x B fp32; bias: n fp32 or None; out_dtype: x's dtype
     (default) or torch.float32; out: an optional tokens x n tensor of that dtype with unit column
-    stride to write into."""
+    stride to write into.  norm=(weight, eps) and residual as in ternary_decode: the norm runs in the
+    gather launch, the residual (which may be `out`) is added where y is converted.  With either the
+    call is pt2q_ternary_skinny_fused, still two launches."""
     what = "ternary_skinny"
     packs, bs = _group_members(x, [(codes, gather, alpha, mu, bias)], block_size, what)
     codes, gather, alpha, mu, bias = packs[0]
     tokens, m = x.shape
     n, B = alpha.shape
     out = _check_out(out, tokens, n, x.dtype if out_dtype is None else out_dtype, x.device, what)
+    if norm is not None or residual is not None:
+        if tokens:
+            _skinny_group(x, packs, bs, [out], _lib.DECODE_PLAIN, norm, [residual], what)
+        return out
     if tokens == 0:
         return out
     lib = _lib.lib()
@@ -241,6 +261,14 @@ def _decode_group(x, packs, block_size, outs, epilogue, what, norm=None, residua
         _lib.check(_lib.lib().pt2q_ternary_decode_group(*args, _lib.stream_of(x.device)), what)
         return
     weight, eps = (None, 0.0) if norm is None else _check_norm(x, norm, caller)
+    residuals = _check_residuals(outs, residuals, caller)
+    res, ldrs = _lib.ptr_array(residuals), ld(residuals)
+    _lib.check(_lib.lib().pt2q_ternary_decode_fused(*args, _lib.ptr(weight), eps, res[0], as_p(ldrs),
+                                                    _lib.stream_of(x.device)), what)
+
+
+def _check_residuals(outs, residuals, caller):
+    """One residual (or None) per out after the checks of a residual= / residuals= keyword."""
     residuals = [None] * len(outs) if residuals is None else list(residuals)
     if len(residuals) != len(outs):
         raise _lib.Pt2qError(f"{caller}: one residual (or None) per output")
@@ -248,9 +276,7 @@ def _decode_group(x, packs, block_size, outs, epilogue, what, norm=None, residua
         if r is not None and (not isinstance(r, torch.Tensor) or not r.is_cuda or r.shape != o.shape or
                               r.dtype != o.dtype or r.stride(1) != 1):
             raise _lib.Pt2qError(f"{caller}: a residual has its output's shape and dtype, with unit column stride")
-    res, ldrs = _lib.ptr_array(residuals), ld(residuals)
-    _lib.check(_lib.lib().pt2q_ternary_decode_fused(*args, _lib.ptr(weight), eps, res[0], as_p(ldrs),
-                                                    _lib.stream_of(x.device)), what)
+    return residuals
 
 
 def _check_out(out, tokens, n, dtype, device, what):
@@ -304,29 +330,43 @@ def ternary_decode_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor]
     return out
 
 
-def _skinny_group(x, packs, block_size, outs, epilogue):
-    """pt2q_ternary_skinny_group on checked members: one gather launch and one GEMM launch."""
+def _skinny_group(x, packs, block_size, outs, epilogue, norm=None, residuals=None, caller=None):
+    """pt2q_ternary_skinny_group on checked members: one gather launch and one GEMM launch.  With
+    norm (weight, eps) or residuals (one tensor or None per out) pt2q_ternary_skinny_fused: the same
+    two launches."""
     tokens, m = x.shape
     count = len(packs)
     lib = _lib.lib()
     ns = (ctypes.c_int * count)(*[p[2].shape[0] for p in packs])
     Bs = (ctypes.c_int * count)(*[p[2].shape[1] for p in packs])
-    ldys = (ctypes.c_int64 * len(outs))(*[t.stride(0) if tokens > 1 else t.shape[1] for t in outs])
+    ld = lambda ts: (ctypes.c_int64 * len(ts))(*[0 if t is None else t.stride(0) if tokens > 1 else t.shape[1] for t in ts])  # noqa: E731
+    ldys = ld(outs)
     arrs = [_lib.ptr_array([p[i] for p in packs]) for i in range(5)] + [_lib.ptr_array(outs)]
     as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    args = (_lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns), arrs[0][0],
+            arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0], _lib.dtype_code(outs[0]),
+            as_p(ldys), epilogue)
+    if norm is not None or residuals is not None:  # checked before the workspace is taken
+        weight, eps = (None, 0.0) if norm is None else _check_norm(x, norm, caller)
+        residuals = _check_residuals(outs, residuals, caller)
+        res, ldrs = _lib.ptr_array(residuals), ld(residuals)
     ws = _lib.workspace(lib.pt2q_ternary_skinny_group_workspace_bytes(tokens, m, count, as_p(ns), epilogue), x.device)
-    _lib.check(lib.pt2q_ternary_skinny_group(
-        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns), arrs[0][0],
-        arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0], _lib.dtype_code(outs[0]),
-        as_p(ldys), epilogue, _lib.ptr(ws), ws.numel(), _lib.stream_of(x.device)), "pt2q_ternary_skinny_group")
+    tail = (_lib.ptr(ws), ws.numel(), _lib.stream_of(x.device))
+    if norm is None and residuals is None:
+        _lib.check(lib.pt2q_ternary_skinny_group(*args, *tail), "pt2q_ternary_skinny_group")
+    else:
+        _lib.check(lib.pt2q_ternary_skinny_fused(*args, _lib.ptr(weight), eps, res[0], as_p(ldrs), *tail),
+                   "pt2q_ternary_skinny_fused")
 
 
 def ternary_skinny_group(x: torch.Tensor, members, out_dtype: Optional[torch.dtype] = None, outs=None,
-                         block_size: Optional[int] = None):
+                         block_size: Optional[int] = None, norm=None, residuals=None):
     """pt2q_ternary_skinny_group, PLAIN: 1..4 ternary linears on the same x (up to 64 tokens; the
     kernel for 2..64) in one gather launch and one GEMM launch -- q/k/v of a batched-decode or
     speculative step.  members, out_dtype, outs and block_size as in ternary_decode_group.  Returns
-    one tokens x n tensor per member, each bit-equal to ternary_skinny on that member alone."""
+    one tokens x n tensor per member, each bit-equal to ternary_skinny on that member alone.
+    norm=(weight, eps) and residuals (one tensor or None per member) as in ternary_decode_group:
+    input_layernorm and q/k/v in the same two launches (pt2q_ternary_skinny_fused)."""
     what = "ternary_skinny_group"
     packs, bs = _group_members(x, members, block_size, what)
     tokens = x.shape[0]
@@ -336,24 +376,25 @@ def ternary_skinny_group(x: torch.Tensor, members, out_dtype: Optional[torch.dty
     outs = [_check_out(None if outs is None else outs[z], tokens, p[2].shape[0], out_dtype, x.device, what)
             for z, p in enumerate(packs)]
     if tokens:
-        _skinny_group(x, packs, bs, outs, _lib.DECODE_PLAIN)
+        _skinny_group(x, packs, bs, outs, _lib.DECODE_PLAIN, norm, residuals, what)
     return outs
 
 
 def ternary_skinny_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor] = None,
-                          block_size: Optional[int] = None) -> torch.Tensor:
+                          block_size: Optional[int] = None, norm=None) -> torch.Tensor:
     """pt2q_ternary_skinny_group, SWIGLU: h = silu(gate(x)) * up(x) for up to 64 tokens in one gather
     launch and one GEMM launch, the activation computed where the K-split partials are summed;
     bit-defined by contract SWIGLU16 from the 16-bit outputs the two separate
     ternary_skinny calls would give.  gate, up: members as in ternary_decode_group, equal widths; h
-    has x's dtype."""
+    has x's dtype.  norm=(weight, eps) as in ternary_decode: post_attention_layernorm in the gather
+    launch (pt2q_ternary_skinny_fused)."""
     what = "ternary_skinny_swiglu"
     packs, bs = _group_members(x, [gate, up], block_size, what)
     if packs[0][2].shape[0] != packs[1][2].shape[0]:
         raise _lib.Pt2qError(f"{what}: gate and up have the same number of rows")
     out = _check_out(out, x.shape[0], packs[0][2].shape[0], x.dtype, x.device, what)
     if x.shape[0]:
-        _skinny_group(x, packs, bs, [out], _lib.DECODE_SWIGLU)
+        _skinny_group(x, packs, bs, [out], _lib.DECODE_SWIGLU, norm, None, what)
     return out
 
 
@@ -526,8 +567,11 @@ class TernaryMLPBlock(nn.Module):
     over a TernaryGatedMLP.  With all three projections at decode="fused", h in their dtype and
     1..min(block_decode_max_tokens, mlp_decode_max_tokens) tokens it takes two launches --
     ternary_decode_swiglu with the norm as prologue, then ternary_decode on down_proj with h as
-    residual -- in place of four (rms_norm, SwiGLU, down_proj, torch's add), with the same bits;
-    every other call is the formula above over the same modules.
+    residual -- in place of four (rms_norm, SwiGLU, down_proj, torch's add), with the same bits.
+    With all three at decode="skinny" and more tokens than that, up to skinny_block_max_tokens, it is
+    ternary_skinny_swiglu with the norm in its gather launch, then ternary_skinny on down_proj with h
+    as residual: four launches in place of six, with the same bits.  Every other call is the formula
+    above over the same modules.
     norm_weight (hidden elements of the projections' dtype) is a buffer: state_dict key
     "norm_weight", beside the children's keys under "mlp."."""
 
@@ -554,7 +598,16 @@ class TernaryMLPBlock(nn.Module):
                 codes, gather, a32, m32, b32 = down._packed
                 y = ternary_decode(a, codes, gather, a32, m32, down.block_size, b32, residual=ht)
                 return y.reshape(h.shape)
-        return h + self.mlp(rms_norm(h.contiguous(), self.norm_weight.to(h.dtype), self.eps))
+        if gate.decode == up.decode == down.decode == "skinny" and h.dtype == gate.dtype == self.norm_weight.dtype:
+            ht = h.reshape(-1, hidden).contiguous()
+            if min(block_decode_max_tokens, mlp_decode_max_tokens) < ht.shape[0] <= skinny_block_max_tokens:
+                if down._packed is None:
+                    down._prepare()
+                a = ternary_skinny_swiglu(ht, gate, up, norm=(self.norm_weight, self.eps))
+                codes, gather, a32, m32, b32 = down._packed
+                y = ternary_skinny(a, codes, gather, a32, m32, down.block_size, b32, residual=ht)
+                return y.reshape(h.shape)
+        return h +self.mlp(rms_norm(h.contiguous(), self.norm_weight.to(h.dtype), self.eps))
 
 
 def _gated_mlp_matches(gate, up, down) -> bool:
