@@ -75,12 +75,14 @@ def weight_int(case, compat):
 def _units(n, m, bs, tokens, seed, compat):
     case = exact_case(n, m, bs, tokens, seed)
     Wi = weight_int(case, compat)
-    xi = case["x_int"].astype(np.int64)
+    # the products in float64 (BLAS; numpy's int64 product takes seconds at 10^4 features): |x| <= 8,
+    # |w| <= 11 and m < 2**40 keep every partial sum an integer below 2**53, so they are exact
+    xi, Wt = case["x_int"].astype(np.float64), Wi.T.astype(np.float64)
     # the bound that makes the data order-free: no partial sum of any subset of the terms of an
     # output, bias included, can reach 2**20 units
-    worst = (np.abs(xi) @ np.abs(Wi).T).max() + 16 * np.abs(case["bias_int"]).max()
+    worst = (np.abs(xi) @ np.abs(Wt)).max() + 16 * np.abs(case["bias_int"]).max()
     assert worst < EXACT_BOUND, (worst, EXACT_BOUND)
-    u = xi @ Wi.T
+    u = (xi @ Wt).astype(np.int64)
     u.setflags(write=False)
     return u
 

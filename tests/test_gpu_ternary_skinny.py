@@ -3,16 +3,25 @@ reduced inside the launch) for 2..64 tokens, through ternary_skinny and TernaryL
 
   1. exact GEMM   exactly summable data (tests/ternary_linear_ref.py): any split, order or tile must
                   give the integer reference's bits; no tolerance
-  2. workspace    a workspace full of 0xFF bytes, and one a previous call left behind, change nothing
+  2. workspace    a workspace full of 0xFF bytes, and one a previous call left behind, change nothing;
+                  problem A, problem B, A again through one workspace, each exact
   3. random data  against float64 within one ulp per accumulation step; eight calls, one result
-  4. routing      which kernel a decode="skinny" module reaches for 1, 2, 64 and 65 tokens
-  5. arguments    refused calls return their status and leave y alone"""
+  4. graph        a captured decode="skinny" call replayed on rewritten x equals the eager bits
+  5. routing      which kernel a decode="skinny" module reaches for 1, 2, 64 and 65 tokens
+  6. arguments    refused calls return their status and leave y alone
+
+The shapes are tests/ternary_skinny_cases.py's: SHAPES for the ragged edges, the scale-block edges and
+every NT, on K slices of 1..3 blocks; LONG and WIDE for slices of 4..7 blocks, which overwrite and lap
+the 3-slot LDS ring, for 16 splits by the clamp, and for many feature tiles, where the split is the
+workgroup target's and the partial tiles outgrow an XCD's L2.  test_ternary_skinny_cases_cpu.py holds
+the tables to those plans."""
 import numpy as np
 import pytest
 import torch
 
 import stream_cases as sc
 import ternary_linear_ref as ref
+from ternary_skinny_cases import LONG, SHAPES, WIDE
 from test_gpu_parity import cuda
 from test_gpu_stream_order import cycles_per_ms, test_entry_on_a_delayed_stream as _delayed_stream  # noqa: F401
 
@@ -37,19 +46,6 @@ def test_stream_order(pt2q, cycles_per_ms):  # noqa: F811
 
 TDT = {"fp16": torch.float16, "bf16": torch.bfloat16}
 GUARD = 64  # fp32 elements of NaN before and after a guarded array
-
-# (n, m, bs, tokens, compat of the fp16 run; bf16 takes the other): splits by ts_plan in brackets
-SHAPES = [
-    (1, 100, 16, 2, False),       # [1] one split, direct store; 16-position tables
-    (40, 100, 128, 5, True),      # per-channel
-    (63, 200, 48, 15, True),      # the table switches inside a block; ragged features and tokens
-    (64, 1100, 80, 16, False),    # [4] exactly one feature tile and one token tile
-    (65, 640, 192, 17, True),     # [2] a second tile of one row in both directions; uneven 2 + 3 blocks
-    (130, 2100, 128, 33, False),  # [8] three token tiles; most splits
-    (200, 1600, 128, 64, True),   # [6] the cap, NT = 4
-    (127, 130, 130, 48, False),   # per-channel, P = 256
-    (40, 2100, 48, 31, False),    # ceil(P / bs) = 46 > B = 44: the padding scale clamp (NaN guards)
-]
 
 
 def _layer(pt2q, c, dtype, compat, decode="skinny"):
@@ -92,9 +88,7 @@ def _case(n, m, bs, tokens, compat16, dtype):
     return ref.exact_case(n, m, bs, tokens, ref.case_seed(n, m, bs, tokens)), compat
 
 
-@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
-@pytest.mark.parametrize("n,m,bs,tokens,compat16", SHAPES)
-def test_exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype):
+def _exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype):
     monkeypatch.setattr(pt2q.ternary, "skinny_max_tokens", 64)
     c, compat = _case(n, m, bs, tokens, compat16, dtype)
     lay = _layer(pt2q, c, dtype, compat)
@@ -106,6 +100,19 @@ def test_exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype):
     for bias in (True, False):
         assert _same(_skinny(pt2q, lay, x, TDT[dtype], bias), ref.exact_reference(c, compat, bias, dtype)), bias
         assert _same(_skinny(pt2q, lay, x, torch.float32, bias), ref.exact_reference(c, compat, bias)), bias
+
+
+@pytest.mark.parametrize("dtype", ["fp16", "bf16"])
+@pytest.mark.parametrize("n,m,bs,tokens,compat16", SHAPES + LONG)
+def test_exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype):
+    _exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype)
+
+
+@pytest.mark.parametrize("n,m,bs,tokens,compat16,dtype", WIDE)
+def test_exact_gemm_many_tiles(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype):
+    """256, 171 and 512 feature tiles: 2 and 3 splits because the workgroup target asks for no more
+    (4-block slices, 6 MiB of partial tiles at the first), and the direct store after a 7-block slice."""
+    _exact_gemm(pt2q, monkeypatch, n, m, bs, tokens, compat16, dtype)
 
 
 @pytest.mark.parametrize("shape", [SHAPES[5], SHAPES[4]])
@@ -122,8 +129,30 @@ def test_workspace_hygiene(pt2q, shape):
         assert _same(y, want)
 
 
+@pytest.mark.parametrize("shape,dtype", [(LONG[3], "fp16"), (WIDE[0][:5], WIDE[0][5])])
+def test_workspace_reuse_across_problems(pt2q, shape, dtype):
+    """A, B, A through one workspace, B the same shapes from another seed (the decoy rule of DESIGN.md
+    §6.4: valid operands everywhere, no poison).  A call that reads a partial tile, a counter or an
+    x_sel row its own launches have not written yet finds the other problem's, and its bits are wrong.
+    Seven-block slices with 16 partials per tile, and the 6 MiB of partials of 256 tiles."""
+    n, m, bs, tokens = shape[:4]
+    a, compat = _case(*shape, dtype)
+    b = ref.exact_case(n, m, bs, tokens, a["seed"] + 1)
+    lays = [_layer(pt2q, c, dtype, compat) for c in (a, b)]
+    wants = [ref.exact_reference(c, compat, True) for c in (a, b)]
+    assert (wants[0] != wants[1]).mean() > 0.9
+    nbytes = pt2q._lib.lib().pt2q_ternary_skinny_workspace_bytes(tokens, n, m)
+    ws = torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+    for k in (0, 1, 0):
+        x = cuda([a, b][k]["x"]).to(TDT[dtype])
+        y = torch.empty((tokens, n), dtype=torch.float32, device=x.device)
+        assert _raw(pt2q, lays[k], x, y, ws, nbytes) == 0
+        assert _same(y, wants[k]), k
+
+
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
-@pytest.mark.parametrize("n,m,bs,tokens", [(130, 2100, 128, 33), (65, 640, 192, 17)])
+@pytest.mark.parametrize("n,m,bs,tokens", [(130, 2100, 128, 33), (65, 640, 192, 17), (65, 13824, 128, 33),
+                                           (16321, 1024, 128, 48)])
 def test_random_against_float64(pt2q, n, m, bs, tokens, dtype):
     """Scales in the range of real layers, x ~ N(0, 1) in TX.  The bound allows one unit in the last
     place (2^-24 relative, doubled to 2^-23 for the rounding of the sum itself) per accumulation
@@ -145,6 +174,27 @@ def test_random_against_float64(pt2q, n, m, bs, tokens, dtype):
     print(f"max err / bound = {(err / bound).max():.3e}")
     assert (err <= bound).all()
     assert all(torch.equal(y, ys[0]) for y in ys[1:])
+
+
+def test_graph_replay(pt2q, monkeypatch):
+    """One decode="skinny" layer call (gather, then the GEMM with its tickets: 16 splits of 7 blocks,
+    NT 4) captured once and replayed on three x written into the captured buffer: the eager bits."""
+    monkeypatch.setattr(pt2q.ternary, "skinny_max_tokens", 64)
+    c, compat = _case(*LONG[3], "fp16")
+    lay = _layer(pt2q, c, "fp16", compat)
+    xs = [(cuda(c["x"]) * s).half() for s in (0.37, 0.61, 1.0)]
+    eager = [lay(x).clone() for x in xs]
+    assert _same(eager[2], ref.exact_reference(c, compat, True, "fp16"))
+    assert not torch.equal(eager[0], eager[1])
+    xg = torch.zeros_like(xs[0])
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        yg = lay(xg)
+    for x, want in zip(xs, eager):
+        xg.copy_(x)
+        graph.replay()
+        assert torch.equal(yg, want)
 
 
 def test_routing(pt2q, monkeypatch):

@@ -4,7 +4,13 @@ ternary_skinny_swiglu and TernaryGatedMLP over decode="skinny" children.
 
 Exact data (tests/ternary_linear_ref.py) with one x for all members: member 0's x_int, every member's
 expected output in integers.  |x_int| <= 8 and |16 w| <= 11, so no partial sum of an output passes
-88 m + 512 units of 1/64, which _units asserts to be below 2**20: any order gives the same fp32 bits."""
+88 m + 512 units of 1/64, which _want asserts to be below 2**20: any order gives the same fp32 bits.
+
+The shapes are tests/ternary_skinny_cases.py's.  PLAIN and SWIGLU: ragged edges, scale-block edges, every
+NT, on K slices of 1..3 blocks.  PLAIN_LONG: a 256-tile member of 2 splits (4-block slices, 6 MiB of
+partial tiles) beside a 2-tile member of 4 splits in one launch, so the first member's tiles see
+workgroups of slices they do not have.  SWIGLU_LONG: 5-block slices and 32 tickets per tile.
+test_ternary_skinny_cases_cpu.py holds the tables to those plans."""
 import ctypes
 
 import numpy as np
@@ -15,6 +21,7 @@ import torch.nn.functional as F
 import stream_cases as sc
 import ternary_linear_ref as ref
 from ternary_group_ref import swiglu
+from ternary_skinny_cases import PLAIN, PLAIN_LONG, SWIGLU, SWIGLU_LONG
 from test_gpu_parity import cuda
 from test_gpu_stream_order import cycles_per_ms, test_entry_on_a_delayed_stream as _delayed_stream  # noqa: F401
 from test_gpu_ternary_skinny import TDT, _layer
@@ -52,18 +59,6 @@ def test_stream_order(pt2q, cycles_per_ms):  # noqa: F811
     _delayed_stream(pt2q, cycles_per_ms, sc.BY_ID["ternary-skinny-group-swiglu"])
 
 
-# (m, bs, tokens, ns): the members' split counts by ts_plan in brackets
-PLAIN = [
-    (100, 16, 2, (1, 40)),              # [1] direct stores
-    (640, 192, 17, (65, 1, 130, 64)),   # [2] uneven 2 + 3 blocks; two token tiles; one- and three-tile members
-    (2100, 48, 33, (40, 130)),          # [8] the table switches inside a block; the padding-scale clamp
-    (1600, 128, 64, (200, 63)),         # [6] NT = 4
-    (130, 130, 48, (127,)),             # per-channel; a group of one
-    (512, 128, 3, (32705, 65)),         # [1, 2] 512 tiles store directly beside a member that takes tickets
-]
-SWIGLU = [(100, 16, 2, 40), (640, 192, 17, 65), (2100, 128, 33, 130), (1600, 128, 64, 200)]
-
-
 def _ints(v, ty=ctypes.c_int):
     return ctypes.cast((ty * len(v))(*v), ctypes.c_void_p)
 
@@ -99,15 +94,16 @@ def _nobias(lay):
 
 
 @pytest.mark.parametrize("m,bs,tokens,ns,dtype", [s + (d,) for s in PLAIN for d in ("fp16", "bf16")
-                                                  if d == "fp16" or s[3][0] != 32705])
+                                                  if d == "fp16" or s[3][0] != 32705] + PLAIN_LONG)
 def test_plain_group_exact(pt2q, m, bs, tokens, ns, dtype):
     compat = dtype == "bf16"
     cases, lays, x_int = _members(pt2q, m, bs, tokens, ns, dtype, compat)
     packs = [lay._packed if z else _nobias(lay) for z, lay in enumerate(lays)]  # member 0 without its bias
+    wants = [_want(c, x_int, compat, z > 0, "fp32") for z, c in enumerate(cases)]  # exact in fp32
     for ydt, out in ((TDT[dtype], dtype), (torch.float32, "fp32")):
         ys = pt2q.ternary_skinny_group(_x(x_int, dtype), packs, out_dtype=ydt, block_size=bs)
-        for z, (c, y) in enumerate(zip(cases, ys)):
-            assert _eq(y, _want(c, x_int, compat, z > 0, out)), (z, out)
+        for z, (w, y) in enumerate(zip(wants, ys)):
+            assert _eq(y, w if out == "fp32" else ref.round16(w, out)), (z, out)
 
 
 @pytest.mark.parametrize("count", [1, 2, 3, 4])
@@ -121,7 +117,7 @@ def test_plain_group_is_the_members_alone(pt2q, m, bs, tokens, ns, count):
 
 
 @pytest.mark.parametrize("dtype", ["fp16", "bf16"])
-@pytest.mark.parametrize("m,bs,tokens,n", SWIGLU)
+@pytest.mark.parametrize("m,bs,tokens,n", SWIGLU + SWIGLU_LONG)
 def test_swiglu_exact(pt2q, m, bs, tokens, n, dtype):
     compat = dtype == "bf16"
     cases, lays, x_int = _members(pt2q, m, bs, tokens, (n, n), dtype, compat)

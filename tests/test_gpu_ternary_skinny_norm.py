@@ -3,7 +3,12 @@ residual epilogue where y is converted, through the norm= / residual(s)= keyword
 ternary_skinny_group and ternary_skinny_swiglu, and TernaryMLPBlock over decode="skinny" children.
 
 The reference is the composition of entries the other test files pin to their numpy restatements:
-rms_norm (RMSNORM16), the plain skinny calls, torch's 16-bit add (RESADD16).  Bit for bit, no tolerance."""
+rms_norm (RMSNORM16), the plain skinny calls, torch's 16-bit add (RESADD16).  Bit for bit, no tolerance.
+
+The shapes are tests/ternary_skinny_cases.py's: NORM_SHAPES and NORM_SWIGLU on rows of m <= 2100, and
+NORM_LONG (a PLAIN group of two on m = 10240) and NORM_RES_LONG (norm and residual, one member, m =
+14336, 64 tokens) for the norm prologue's 512 threads on rows of 20 and 28 elements per thread, in front
+of K slices of 5 and 7 blocks."""
 import ctypes
 
 import numpy as np
@@ -15,14 +20,13 @@ import ternary_linear_ref as ref
 import ternary_norm_ref as nref
 from test_gpu_stream_order import cycles_per_ms, test_entry_on_a_delayed_stream as _delayed_stream  # noqa: F401
 from test_gpu_ternary_skinny import TDT, _layer
-from test_gpu_ternary_skinny_group import PLAIN, _ints, _lone, _members, _x
+from ternary_skinny_cases import NORM_LONG, NORM_RES_LONG, NORM_SHAPES as SHAPES, NORM_SWIGLU as SWIGLU, PLAIN
+from test_gpu_ternary_skinny_group import _ints, _lone, _members, _x
 
 pytestmark = pytest.mark.gpu
 
 EPS = 1e-5
 DTYPES = ["fp16", "bf16"]
-SHAPES = [PLAIN[0], PLAIN[1], PLAIN[2], PLAIN[4]]  # (m, bs, tokens, ns): see the table there
-SWIGLU = [(100, 16, 2, 40), (640, 192, 17, 65), (1600, 128, 64, 200)]
 E_ARG, E_UNSUPPORTED = 1, 3
 # Stream order (appended at collection, as the two skinny test files do): PLAIN with norm and
 # residuals, 17 tokens, two K slices per member.
@@ -75,7 +79,7 @@ def _res(y, seed):
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
-@pytest.mark.parametrize("m,bs,tokens,ns", SHAPES)
+@pytest.mark.parametrize("m,bs,tokens,ns", SHAPES + [NORM_LONG])
 def test_norm_plain_group(pt2q, m, bs, tokens, ns, dtype):
     _, lays, x, w = _setup(pt2q, m, bs, tokens, ns, dtype)
     if m == 640:  # ldx > m and a base that is only 2-byte aligned
@@ -117,13 +121,23 @@ def test_residual_plain_group(pt2q, m, bs, tokens, ns, dtype):
     assert torch.equal(y0, rs[0] + alone[0])
 
 
-@pytest.mark.parametrize("dtype", DTYPES)
-def test_norm_and_residual(pt2q, dtype):
-    _, lays, x, w = _setup(pt2q, *PLAIN[1], dtype)
+def _norm_and_residual(pt2q, shape, dtype):
+    _, lays, x, w = _setup(pt2q, *shape, dtype)
     xn = pt2q.rms_norm(x, w, EPS)
     rs = [_res(_lone(pt2q, lay, x), 80 + z) for z, lay in enumerate(lays)]
     for lay, y, r in zip(lays, pt2q.ternary_skinny_group(x, lays, norm=(w, EPS), residuals=rs), rs):
         assert torch.equal(y, r + _lone(pt2q, lay, xn))
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_and_residual(pt2q, dtype):
+    _norm_and_residual(pt2q, PLAIN[1], dtype)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_norm_and_residual_long_rows(pt2q, dtype):
+    """One member, m = 14336, 64 tokens: 28 elements per thread of the norm, then 16 slices of 7 blocks."""
+    _norm_and_residual(pt2q, NORM_RES_LONG, dtype)
 
 
 @pytest.mark.parametrize("dtype", DTYPES)
