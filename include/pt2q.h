@@ -466,6 +466,37 @@ int pt2q_ternary_skinny_group(const void* x, int xdtype, int tokens, int64_t ldx
                               void* const* y, int ydtype, const int64_t* ldy, int epilogue,
                               void* workspace, size_t workspace_bytes, void* stream);
 
+/* The grouped form of pt2q_ternary_linear's prefill kernel (256 tokens and up;
+ * csrc/ternary_prefill.hip): count (1 .. PT2Q_DECODE_GROUP_MAX) packed ternary linears that read the
+ * same x in ONE gather launch and ONE GEMM launch: two launches, no synchronisation, capturable.  The
+ * argument list, the argument rules and the status codes are pt2q_ternary_skinny_group's (host arrays
+ * read during the call only, count 1 .. 4, SWIGLU with count 2, n[0] = n[1] and a 16-bit y, the
+ * workspace 256-byte aligned), with a workspace of
+ * pt2q_ternary_prefill_group_workspace_bytes(tokens, m, count) bytes (0 for arguments the call would
+ * refuse): one gathered copy of x per member.  Differences: any tokens >= 1 is served (this is the
+ * kernel for 256 and up; small counts are legal so that a caller needs no second path);
+ * PT2Q_E_UNSUPPORTED when bs < m and bs % 128 != 0, or when a codes[z] is not 16-byte aligned.  Every
+ * check runs before anything is launched.  Nothing is read from what an earlier call left in the
+ * workspace.  Bit contract:
+ *   PT2Q_DECODE_PLAIN   y[z] holds what pt2q_ternary_linear writes for member z alone wherever that
+ *                       call takes the prefill kernel (tokens >= 256 and bs >= m or bs % 128 == 0),
+ *                       bit for bit: every output element is one chain of 32x32x16 MFMAs over the
+ *                       128-position blocks in ascending order, position 128 kb + 16 g + 8 h + j in
+ *                       k-slot (h, j) of step g, then one fp32 bias add and one rounding to ydtype.  At
+ *                       fewer tokens it is the same single ascending chain (pt2q_ternary_linear splits
+ *                       K there, so its last bits differ).
+ *   PT2Q_DECODE_SWIGLU  member 0 the gate, member 1 the up projection; only y[0] / ldy[0] are used:
+ *                       y[0] holds SWIGLU16 of the two members' 16-bit outputs so
+ *                       defined, RN_TY(RN_TY(g * sigmoid(g)) * u), bit for bit; g and u are never
+ *                       written to memory.  Non-finite g or u give an unspecified value. */
+size_t pt2q_ternary_prefill_group_workspace_bytes(int tokens, int m, int count);
+int pt2q_ternary_prefill_group(const void* x, int xdtype, int tokens, int64_t ldx, int m, int count,
+                               const int* n, const uint8_t* const* codes, const int* const* gather,
+                               const float* const* alpha, const float* const* mu, const int* B, int bs,
+                               const float* const* bias /* array or entries nullable */,
+                               void* const* y, int ydtype, const int64_t* ldy, int epilogue,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 /* y[t] = RMSNorm(x[t]) by contract RMSNORM16: the Llama form
  * weight * (x.float() * rsqrt(mean(x²) + eps)).to(xdtype), bit-defined -- 512 fmaf chains over the
  * elements i ≡ j (mod 512), a butterfly per 64 of them, the eight sums added in order, a correctly

@@ -17,6 +17,9 @@ Drop-in for the reference's hot-path surface:
                                              (its grouped form: projections sharing x, gate/up + SwiGLU, 2-64 tokens;
                                               norm= and residual(s)= on all three: RMSNorm in the gather launch,
                                               the residual add where y is converted)
+    ternary_prefill_group, ternary_prefill_swiglu
+                                             (the prefill kernel's grouped form: q/k/v, gate/up + SwiGLU, 256+ tokens;
+                                              TernaryGatedMLP(prefill="fused"), fuse_gated_mlp(prefill="fused"))
     ternary_decode_group, ternary_decode_swiglu, TernaryGatedMLP, fuse_gated_mlp
                                              (projections sharing x, and gate/up + SwiGLU, in one launch)
     rms_norm, TernaryMLPBlock                (RMSNorm as a kernel and as the decode kernel's prologue,
@@ -36,7 +39,7 @@ from .calibration import (GramAccumulator, GramCapture, find_linear_layers, get_
 from .ternary import (TernaryGatedMLP, TernaryLinear, TernaryMLPBlock, compute_bits_per_weight, fuse_gated_mlp,
                       load_quantized_model, replace_linear_with_ternary, rms_norm, save_quantized_model, set_decode,
                       ternary_decode, ternary_decode_group, ternary_decode_swiglu, ternary_skinny,
-                      ternary_skinny_group, ternary_skinny_swiglu)
+                      ternary_skinny_group, ternary_skinny_swiglu, ternary_prefill_group, ternary_prefill_swiglu)
 from .evaluation import evaluate_perplexity
 from .engine import (LayerGraph, LayerOutput, LayerWorkspace, UnitRun, UnitWorkspace, cholesky_inverse,
                      dequantize, error_feedback, fill_synthetic, gram, hessian_inverse, pack_ternary, prepare_hessian,
@@ -58,5 +61,5 @@ __all__ = [
     "compute_block_variance", "LayerReport", "layer_report", "quadform_rows", "compute_output_error_from_gram",
     "ternary_decode", "set_decode", "ternary_decode_group", "ternary_decode_swiglu", "TernaryGatedMLP",
     "fuse_gated_mlp", "rms_norm", "TernaryMLPBlock", "ternary_skinny", "ternary_skinny_group",
-    "ternary_skinny_swiglu",
+    "ternary_skinny_swiglu", "ternary_prefill_group", "ternary_prefill_swiglu",
 ]

@@ -106,6 +106,8 @@ _SIGS = {
     "pt2q_ternary_skinny": (I, [P, I, I, I64, I, I, P, P, P, P, I, I, P, P, I, I64, P, SZ, P]),
     "pt2q_ternary_skinny_group_workspace_bytes": (SZ, [I, I, I, P, I]),
     "pt2q_ternary_skinny_group": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, SZ, P]),
+    "pt2q_ternary_prefill_group_workspace_bytes": (SZ, [I, I, I]),
+    "pt2q_ternary_prefill_group": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, SZ, P]),
     "pt2q_rmsnorm": (I, [P, I, I, I64, I, P, F, P, I64, P]),
     "pt2q_ternary_decode_fused": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, F, P, P, P]),
     "pt2q_ternary_skinny_fused": (I, [P, I, I, I64, I, I, P, P, P, P, P, P, I, P, P, I, P, I, P, F, P, P, P, SZ, P]),

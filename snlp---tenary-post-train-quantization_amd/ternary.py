@@ -94,6 +94,19 @@ skinny_mlp_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SK
 SKINNY_BLOCK_CROSSOVER_TOKENS = 64
 skinny_block_max_tokens = min(int(_lib.lib().pt2q_ternary_skinny_max_tokens()), SKINNY_BLOCK_CROSSOVER_TOKENS)
 
+PREFILL_MODES = ("children", "fused")
+# Smallest token count a TernaryGatedMLP(prefill="fused") runs as ternary_prefill_swiglu + down_proj
+# (two gathers, the pair GEMM, down: gate(x) and up(x) never reach memory) in place of
+# down(F.silu(gate(x)) * up(x)); None: never.  PREFILL_MLP_CROSSOVER_TOKENS is the smallest token count of
+# profiles/ternary_prefill_group_timing.txt from which that form is below the children form by more than
+# the repeats' spread at every measured shape and dtype, and never below 65 (up to 64
+# tokens the skinny kernels serve).  Measured (hidden 4096 / 11008 and 5120 / 13824, fp16 and bf16, 128 ..
+# 4096 tokens): 18 .. 82 us below at 128, 256 and 512 tokens, but 26 .. 261 us (4 .. 14 %) ABOVE the children
+# form at 1024, 2048 and 4096 at every shape and dtype, so no count qualifies: None, the module never
+# routes there as shipped.  A caller whose prompts stay at 512 tokens or fewer may set prefill_mlp_min_tokens.
+PREFILL_MLP_CROSSOVER_TOKENS = None
+prefill_mlp_min_tokens = PREFILL_MLP_CROSSOVER_TOKENS
+
 
 def _check_mode(decode):
     if decode not in DECODE_MODES:
@@ -398,6 +411,59 @@ def ternary_skinny_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor]
     return out
 
 
+def _prefill_group(x, packs, block_size, outs, epilogue):
+    """pt2q_ternary_prefill_group on checked members: one gather launch and one GEMM launch."""
+    tokens, m = x.shape
+    count = len(packs)
+    lib = _lib.lib()
+    ns = (ctypes.c_int * count)(*[p[2].shape[0] for p in packs])
+    Bs = (ctypes.c_int * count)(*[p[2].shape[1] for p in packs])
+    ldys = (ctypes.c_int64 * len(outs))(*[t.stride(0) if tokens > 1 else t.shape[1] for t in outs])
+    arrs = [_lib.ptr_array([p[i] for p in packs]) for i in range(5)] + [_lib.ptr_array(outs)]
+    as_p = lambda a: ctypes.cast(a, ctypes.c_void_p)  # noqa: E731
+    ws = _lib.workspace(lib.pt2q_ternary_prefill_group_workspace_bytes(tokens, m, count), x.device)
+    _lib.check(lib.pt2q_ternary_prefill_group(
+        _lib.ptr(x), _lib.dtype_code(x), tokens, x.stride(0) if tokens > 1 else m, m, count, as_p(ns), arrs[0][0],
+        arrs[1][0], arrs[2][0], arrs[3][0], as_p(Bs), block_size, arrs[4][0], arrs[5][0], _lib.dtype_code(outs[0]),
+        as_p(ldys), epilogue, _lib.ptr(ws), ws.numel(), _lib.stream_of(x.device)), "pt2q_ternary_prefill_group")
+
+
+def ternary_prefill_group(x: torch.Tensor, members, out_dtype: Optional[torch.dtype] = None, outs=None,
+                          block_size: Optional[int] = None):
+    """pt2q_ternary_prefill_group, PLAIN: 1..4 ternary linears on the same x (any token count; the
+    kernel for 256 and up) in one gather launch and one GEMM launch -- q/k/v of a prompt.  members,
+    out_dtype, outs and block_size as in ternary_decode_group; the block size is at least m or a
+    multiple of 128.  Returns one tokens x n tensor per member, each bit-equal to what the MFMA path
+    of TernaryLinear gives for that member alone at 256 tokens and up."""
+    what = "ternary_prefill_group"
+    packs, bs = _group_members(x, members, block_size, what)
+    tokens = x.shape[0]
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    if outs is not None and len(outs) != len(packs):
+        raise _lib.Pt2qError(f"{what}: one out per member")
+    outs = [_check_out(None if outs is None else outs[z], tokens, p[2].shape[0], out_dtype, x.device, what)
+            for z, p in enumerate(packs)]
+    if tokens:
+        _prefill_group(x, packs, bs, outs, _lib.DECODE_PLAIN)
+    return outs
+
+
+def ternary_prefill_swiglu(x: torch.Tensor, gate, up, out: Optional[torch.Tensor] = None,
+                           block_size: Optional[int] = None) -> torch.Tensor:
+    """pt2q_ternary_prefill_group, SWIGLU: h = silu(gate(x)) * up(x) for a prompt in one gather launch
+    and one GEMM launch; gate(x) and up(x) are never written to memory.  Bit-defined by contract
+    SWIGLU16 from the 16-bit outputs the MFMA path gives for gate and up alone at 256
+    tokens and up.  gate, up: members as in ternary_decode_group, equal widths; h has x's dtype."""
+    what = "ternary_prefill_swiglu"
+    packs, bs = _group_members(x, [gate, up], block_size, what)
+    if packs[0][2].shape[0] != packs[1][2].shape[0]:
+        raise _lib.Pt2qError(f"{what}: gate and up have the same number of rows")
+    out = _check_out(out, x.shape[0], packs[0][2].shape[0], x.dtype, x.device, what)
+    if x.shape[0]:
+        _prefill_group(x, packs, bs, [out], _lib.DECODE_SWIGLU)
+    return out
+
+
 class TernaryLinear(nn.Module):
     """model.py:17-127.  decode="fused": forwards of 1..decode_max_tokens tokens run the
     single-launch kernel (ternary_decode); decode="skinny": those as well, and forwards of
@@ -530,17 +596,31 @@ class TernaryGatedMLP(nn.Module):
     ternary_decode on down_proj -- in place of three launches and two elementwise kernels.  With
     all three at decode="skinny", forwards of mlp_decode_max_tokens + 1 .. skinny_mlp_max_tokens
     tokens are ternary_skinny_swiglu, then ternary_skinny on down_proj (four launches in place of
-    eight).  Every other call goes through the children exactly as the unfused MLP does."""
+    eight).  prefill="fused" (default "children"), in any decode mode: forwards of at least
+    prefill_mlp_min_tokens tokens are ternary_prefill_swiglu, then down_proj's own forward.  Every other
+    call goes through the children exactly as the unfused MLP does."""
 
-    def __init__(self, gate_proj: TernaryLinear, up_proj: TernaryLinear, down_proj: TernaryLinear):
+    def __init__(self, gate_proj: TernaryLinear, up_proj: TernaryLinear, down_proj: TernaryLinear,
+                 prefill: str = "children"):
         super().__init__()
         if not _gated_mlp_matches(gate_proj, up_proj, down_proj):
             raise _lib.Pt2qError("TernaryGatedMLP: gate_proj and up_proj are TernaryLinear of one shape, dtype and "
                                  "block size, and down_proj reads their width in that dtype")
+        if prefill not in PREFILL_MODES:
+            raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {prefill!r}")
         self.gate_proj, self.up_proj, self.down_proj = gate_proj, up_proj, down_proj
+        self.prefill = prefill
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         gate, up, down = self.gate_proj, self.up_proj, self.down_proj
+        # prefill="fused", in any decode mode: a prompt's gate, up and activation in two launches.  A block
+        # size the entry refuses (below m and no multiple of 128) goes through the children.
+        if self.prefill == "fused" and prefill_mlp_min_tokens is not None and gate.dtype == up.dtype == down.dtype and \
+                (gate.block_size >= gate.in_features or gate.block_size % 128 == 0):
+            xt = x.reshape(-1, gate.in_features).to(gate.dtype).contiguous()
+            if xt.shape[0] >= prefill_mlp_min_tokens:
+                h = ternary_prefill_swiglu(xt, gate, up)
+                return down(h).reshape(*x.shape[:-1], down.out_features)
         if gate.decode == up.decode == down.decode == "fused":
             xt = x.reshape(-1, gate.in_features).to(gate.dtype).contiguous()
             if 0 < xt.shape[0] <= mlp_decode_max_tokens:
@@ -633,12 +713,14 @@ def _computes_silu(act_fn) -> bool:
     return isinstance(r, torch.Tensor) and r.shape == p.shape and torch.equal(r, F.silu(p))
 
 
-def fuse_gated_mlp(model: nn.Module) -> nn.Module:
+def fuse_gated_mlp(model: nn.Module, prefill: str = "children") -> nn.Module:
     """Replace every gated MLP of `model` by a TernaryGatedMLP over the same children: a module
     whose children are TernaryLinear gate_proj, up_proj and down_proj of matching dtypes, widths
     and block sizes (plus at most its act_fn), with no tensors of its own and an act_fn that
     computes SiLU.  Everything else -- attention, an MLP with another activation -- is left as it
-    is; state_dict keys do not change."""
+    is; state_dict keys do not change.  prefill: TernaryGatedMLP's keyword."""
+    if prefill not in PREFILL_MODES:
+        raise ValueError(f"prefill must be one of {PREFILL_MODES}, got {prefill!r}")
     for parent in list(model.modules()):
         for name, mod in list(parent.named_children()):
             kids = dict(mod.named_children())
@@ -648,7 +730,7 @@ def fuse_gated_mlp(model: nn.Module) -> nn.Module:
                 continue
             gate, up, down = kids["gate_proj"], kids["up_proj"], kids["down_proj"]
             if _gated_mlp_matches(gate, up, down) and _computes_silu(getattr(mod, "act_fn", None)):
-                setattr(parent, name, TernaryGatedMLP(gate, up, down))
+                setattr(parent, name, TernaryGatedMLP(gate, up, down, prefill=prefill))
     return model
 
 
